@@ -15,10 +15,21 @@ own chunks — the reduction partitions into independent units, so there is no
 data-path collective ("scaling": "weak"); torch.distributed's gloo backend is
 used only for the harness barrier and the max-over-ranks time.
 
-Also reported (rank 0, N=1 only): the reference's own gloo::sum<float>
-(oracle/_ref, built from /root/reference as it ships) timed on the host cores
-(`cpu_baseline`), and the host-staged rate of a chunk that starts and ends in
-pinned host memory (H2D + kernel + D2H).
+A plain run does only that: set up, warm up, time the K steps, write the
+outputs if --dump-outputs is given, print the JSON line.  Everything else is
+behind --full:
+  N = 1 (rank 0): the stripped 2R + 1W streaming ceiling timed beside the
+  product kernel (`roofline.ceiling`), the reference's own gloo::sum<float>
+  (oracle/_ref, built from the reference's sources as they ship) timed on the
+  host cores (`cpu_baseline`), and the host-staged rate of a chunk that starts
+  and ends in pinned host memory (H2D + kernel + D2H, `host_staged`);
+  N > 1: the xGMI collectives (`xgmi_allreduce`, `per_gpu_efficiency`).
+
+--dump-outputs DIR writes what the last timed step computed (the in-place
+destination chunk a caller of gloo_hip_reduce gets back) as DIR/<name>.npy,
+at the lanes whose inputs are finite (the 0.67 % seeded with +-inf stay +-inf
+whatever the build, and are left out).  The inputs are seeded, so the same arguments give the same arrays from run to
+run and two builds can be compared output for output.
 """
 import argparse
 import contextlib
@@ -43,6 +54,11 @@ def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1000)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the streaming ceiling, host_staged and "
+                        "cpu_baseline at N = 1, the xGMI collectives at N > 1")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's result as DIR/<name>.npy (float32)")
     p.add_argument("--config3-variants", default="",
                    help="N>1: comma list of config-3 variants after the default (diagnosis)")
     p.add_argument("--config3-only", action="store_true",
@@ -1017,6 +1033,52 @@ class HipEvent:
             self.h = ctypes.c_void_p()
 
 
+DUMP_MAX_ELEMENTS = 8 << 20   # 32 MiB of float32 per array
+DUMP_SAMPLE_SEED = 20240
+
+
+# The inputs' special lanes: every SPECIAL_EVERY-th element of
+# dst from offset SPECIAL_OFFSETS[0] and of src from SPECIAL_OFFSETS[1] holds
+# SPECIALS in turn.
+SPECIALS = (0.0, -0.0, 1e-40, -1e-40, float("inf"), float("-inf"))
+SPECIAL_EVERY = 100
+SPECIAL_OFFSETS = (0, 50)
+
+
+def finite_input_lanes(n):
+    """Sorted positions of an n-element chunk at which neither operand was
+    seeded with +-inf, known from how the inputs are laid out (never from the
+    results).  The other lanes hold +-inf from the first step on by
+    construction, so they say nothing when two builds are compared, and a
+    dump is made of finite numbers only."""
+    import numpy as np
+    finite = np.ones(n, dtype=bool)
+    inf_slots = [i for i, v in enumerate(SPECIALS) if v in (float("inf"), float("-inf"))]
+    for off in SPECIAL_OFFSETS:
+        special = np.arange(off, n, SPECIAL_EVERY)          # lane j of these holds SPECIALS[j % len]
+        slot = np.arange(len(special)) % len(SPECIALS)
+        finite[special[np.isin(slot, inf_slots)]] = False
+    return np.nonzero(finite)[0]
+
+
+def dump_outputs(torch, dirname, name, t, lanes=None):
+    """Write device tensor `t` as dirname/name.npy (float32).  `lanes`: the
+    sorted positions that may be written (default: all).  They are all
+    written when there are at most DUMP_MAX_ELEMENTS of them, else
+    DUMP_MAX_ELEMENTS of them drawn once from a fixed seed (sorted, the same
+    positions in every run and every build)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    pos = np.arange(t.numel(), dtype=np.int64) if lanes is None else np.asarray(lanes, dtype=np.int64)
+    if len(pos) > DUMP_MAX_ELEMENTS:
+        pos = pos[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, len(pos), DUMP_MAX_ELEMENTS))]
+    if len(pos) != t.numel():
+        t = t[torch.from_numpy(pos).to(t.device)]
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, t.cpu().numpy().astype(np.float32, copy=False))
+    return path
+
+
 def watchdog_line(out, partial, reason, efficiency, tries=5):
     """The JSON line a firing watchdog prints.  It runs on the watchdog thread
     while the main thread may still be filling `partial`, so a snapshot can
@@ -1089,10 +1151,10 @@ def main():
     pairs = [(torch.rand(n, device=dev, generator=g) * 2 - 1,
               torch.rand(n, device=dev, generator=g) * 2 - 1) for _ in range(args.pairs)]
     # 1 % of the lanes hold +-0, denormals and +-inf
-    specials = torch.tensor([0.0, -0.0, 1e-40, -1e-40, float("inf"), float("-inf")], device=dev)
+    specials = torch.tensor(SPECIALS, device=dev)
     for d, s in pairs:
-        for t, off in ((d, 0), (s, 50)):
-            idx = torch.arange(off, n, 100, device=dev)
+        for t, off in zip((d, s), SPECIAL_OFFSETS):
+            idx = torch.arange(off, n, SPECIAL_EVERY, device=dev)
             t[idx] = specials[torch.arange(idx.numel(), device=dev) % specials.numel()]
     stream = torch.cuda.current_stream(dev)
     sh = stream.cuda_stream
@@ -1153,10 +1215,19 @@ def main():
         per_rank_kernel_ms = [kern_ms]
     tmax = float(t_local[0])
 
+    # what the last timed step left in its destination chunk (before the
+    # ceiling kernel below reduces into the same buffers), at the lanes whose
+    # inputs are finite: the dump holds finite numbers only
+    dumped = None
+    if args.dump_outputs and args.steps >= 1:
+        last_dst = pairs[(args.steps - 1) % len(pairs)][0]
+        dumped = dump_outputs(torch, args.dump_outputs, "dst_last" if world == 1 else f"dst_last_rank{rank}",
+                              last_dst, finite_input_lanes(n))
+
     # the access mix's streaming ceiling, same run, same buffers, after the
     # timed region (in the driver-run line)
     ceiling = None
-    if world == 1 and args.steps >= 2:
+    if args.full and world == 1 and args.steps >= 2:
         try:
             ceiling = stream_ceiling(torch, dev, stream, pairs, n, args.steps)
         except (OSError, RuntimeError) as e:  # pragma: no cover
@@ -1200,7 +1271,10 @@ def main():
             "per_gpu_gib_s": round(value / world, 2),
             "kernel_gib_s": round(alg_bytes / (kern_ms / 1e3) / GIB, 2),
         }
-        if world == 1:
+        out["full"] = args.full
+        if dumped:
+            out["dumped_outputs"] = [os.path.basename(dumped)]
+        if world == 1 and args.full:
             if ceiling and "achieved_gbs" in ceiling:
                 out["roofline"]["ceiling_gbs"] = ceiling["achieved_gbs"]
                 out["roofline"]["frac_of_ceiling"] = round(achieved_gbs / ceiling["achieved_gbs"], 4)
@@ -1210,7 +1284,7 @@ def main():
             if not args.no_cpu:
                 out["cpu_baseline"] = cpu_baseline(args, n)
 
-    if world > 1 and not args.no_allreduce:
+    if world > 1 and args.full and not args.no_allreduce:
         # A failure in the collective must never cost the headline line: every
         # rank arms a watchdog; if it fires, rank 0 prints the headline with
         # the section marked as timed out, and the process exits.

@@ -10,7 +10,7 @@ order=${3:-ring_memcpy,ring_kernel,mesh_memcpy_forked,ring_kernel}
 mkdir -p gpurun_out
 for i in $(seq 1 "$reps"); do
   GLOO_AMD_IPC_DIAG=1 timeout -k 10 240 \
-    python -u bench.py --gpus 2 --steps 5 --warmup 2 --config3-only --config3-variants "$order" \
+    python -u bench.py --gpus 2 --steps 5 --warmup 2 --full --config3-only --config3-variants "$order" \
     > gpurun_out/${tag}_$i.out 2> gpurun_out/${tag}_$i.err
   rc=$?
   echo "run $i rc $rc"
