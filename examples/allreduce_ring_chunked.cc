@@ -66,13 +66,17 @@ int main(int argc, char** argv) {
         algo.run();
       }
       verify(d);
-      // the reference's HD signature (streams, pipelineBroadcastAndReduce)
+      // the reference's HD signature (streams, pipelineBroadcastAndReduce):
+      // the flag selects the pipelined order, which differs from the plain
+      // one with more than one pointer (the second contributes zeros here)
       load();
+      (void)hipMemset(o, 0, count * sizeof(float));
       {
-        gloo_amd::HipAllreduceHalvingDoubling<float> hd(ctx, {d}, count, {}, true);
+        gloo_amd::HipAllreduceHalvingDoubling<float> hd(ctx, {d, o}, count, {}, true);
         hd.run();
       }
       verify(d);
+      verify(o);
       // new-style gloo::allreduce(opts) with BCUBE, separate input and output
       load();
       {

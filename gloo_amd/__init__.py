@@ -237,7 +237,10 @@ ReductionFunction.min = ReductionFunction(ReductionType.MIN)
 # ---- contexts and algorithms (GPU allreduce / reduce-scatter drop-ins) -----
 
 ALGORITHMS = {"ring_chunked": 0, "halving_doubling": 1, "ring": 2, "local": 3,
-              "reduce_scatter": 4, "bcube": 10}  # bcube: AllreduceBcube, recv_elems = [base]
+              "reduce_scatter": 4, "bcube": 10,  # bcube: AllreduceBcube, recv_elems = [base]
+              # CudaAllreduceHalvingDoubling with pipelineBroadcastAndReduce = true
+              # (GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED): always on the reference's route
+              "halving_doubling_pipelined": 11}
 
 
 def _bind_collectives(L):
@@ -489,7 +492,8 @@ class AllreduceOptions(ctypes.Structure):
 
 
 lib.gloo_hip_allreduce.argtypes = [ctypes.c_void_p, ctypes.POINTER(AllreduceOptions)]
-EXPORTED = EXPORTED + ("gloo_hip_allreduce", "gloo_hip_plan_ex", "gloo_hip_interp_batches")
+EXPORTED = EXPORTED + ("gloo_hip_allreduce", "gloo_hip_plan_ex", "gloo_hip_interp_batches",
+                       "gloo_hip_interp_batches_ex")
 
 
 ALLREDUCE_ALGORITHMS = {"ring": 1, "bcube": 2}  # AllreduceOptions::Algorithm (gloo/allreduce.h:38-42)

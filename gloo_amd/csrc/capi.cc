@@ -185,13 +185,14 @@ int gloo_hip_algorithm_create(gloo_hip_context_t ctx, int algo, int op, int dtyp
                                       GLOO_HIP_WORKSPACE_DEVICE, out);
 }
 
-int gloo_hip_interp_batches(const gloo_hip_interp_desc_t* steps, int n, int* defer_out) {
-  if (n < 0 || (n > 0 && (!steps || !defer_out)))
+namespace {
+int interpBatches(const gloo_hip_interp_desc_t* steps, const gloo_hip_interp_desc_ex_t* ex, int n, int* defer_out) {
+  if (n < 0 || (n > 0 && ((!steps && !ex) || !defer_out)))
     return gloo_amd::setError(GLOO_HIP_EINVAL_ARG, "gloo_hip_interp_batches: bad arguments");
   return guarded([&] {
     std::vector<gloo_amd::InterpStep> v((size_t)n);
     for (int i = 0; i < n; i++) {
-      const gloo_hip_interp_desc_t& d = steps[i];
+      const gloo_hip_interp_desc_t& d = ex ? ex[i].step : steps[i];
       GLOO_AMD_ENFORCE(d.kind >= gloo_amd::kInterpCopy && d.kind <= gloo_amd::kInterpFold && d.nsrc >= 0 &&
                            d.nsrc <= GLOO_HIP_MAX_SRCS,
                        "gloo_hip_interp_batches: bad step ", i);
@@ -202,10 +203,26 @@ int gloo_hip_interp_batches(const gloo_hip_interp_desc_t* steps, int n, int* def
       t.dst = reinterpret_cast<char*>(d.dst);
       for (int j = 0; j < GLOO_HIP_MAX_SRCS; j++) t.src[j] = reinterpret_cast<const char*>(d.src[j]);
       t.n = d.bytes;
+      if (ex) {
+        const bool data = d.kind == gloo_amd::kInterpCopy;
+        GLOO_AMD_ENFORCE(ex[i].nxdst >= 0 && ex[i].nxdst <= (data ? gloo_amd::kMaxCopyEntries : 0),
+                         "gloo_hip_interp_batches_ex: bad destination count of step ", i);
+        t.nxdst = ex[i].nxdst;
+        for (int j = 0; j < t.nxdst; j++) t.xdst[j] = reinterpret_cast<char*>(ex[i].xdst[j]);
+      }
     }
     gloo_amd::markInterpBatches(v.data(), v.size(), 1);
     for (int i = 0; i < n; i++) defer_out[i] = v[(size_t)i].flags & gloo_amd::kInterpDefer ? 1 : 0;
   });
+}
+}  // namespace
+
+int gloo_hip_interp_batches(const gloo_hip_interp_desc_t* steps, int n, int* defer_out) {
+  return interpBatches(steps, nullptr, n, defer_out);
+}
+
+int gloo_hip_interp_batches_ex(const gloo_hip_interp_desc_ex_t* steps, int n, int* defer_out) {
+  return interpBatches(nullptr, steps, n, defer_out);
 }
 
 int gloo_hip_ipc_stats(uint64_t* out) {

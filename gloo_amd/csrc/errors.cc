@@ -6,6 +6,7 @@
 
 #include "gloo_amd.h"
 #include "gloo_amd/common.h"
+#include "gloo_amd/plan.h"
 
 namespace gloo_amd {
 namespace {
@@ -22,6 +23,10 @@ int setError(int code, const std::string& msg) {
   std::snprintf(g_last_error, sizeof(g_last_error), "%s", msg.c_str());
   return code;
 }
+namespace {
+// the planners' refusals become the last-error text (plan.h planErrorSink)
+const bool g_plan_sink = (planErrorSink = [](int code, const char* msg) { (void)setError(code, msg); }, true);
+}  // namespace
 }  // namespace gloo_amd
 
 extern "C" const char* gloo_hip_last_error(void) { return gloo_amd::g_last_error; }

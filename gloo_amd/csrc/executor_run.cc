@@ -66,6 +66,40 @@ void deviceMove(char* dst, const char* src, size_t bytes, hipStream_t s) {
 }
 }  // namespace
 
+namespace {
+// The step pairs of the pipelined halving-doubling's per-range local steps
+// (plan.cc) that the executor runs as one pass; that plan only (other plans
+// with ranged local steps, the new-style collectives, keep their launches),
+// built-in ops with device signalling.
+//
+// LOCAL_REDUCE(R) directly followed by the SEND of exactly R from output 0.
+bool foldsIntoSend(const std::vector<Step>& steps, size_t i) {
+  if (i + 1 >= steps.size()) return false;
+  const Step &s = steps[i], &t = steps[i + 1];
+  return s.kind == GLOO_HIP_STEP_LOCAL_REDUCE && !(s.flags & GLOO_HIP_FROM_INPUTS) && s.length > 0 &&
+         t.kind == GLOO_HIP_STEP_SEND && !(t.flags & (GLOO_HIP_SRC_ARENA | GLOO_HIP_FROM_INPUTS)) &&
+         t.src_off == s.dst_off && t.length == s.length;
+}
+// LOCAL_REDUCE(R), WAIT_RECV, REDUCE(R <- inbox) with room for the inbox as
+// the fold's last source.
+bool foldsWithReceive(const std::vector<Step>& steps, size_t i, size_t nptrs) {
+  if (i + 2 >= steps.size() || nptrs < 2 || nptrs + 1 > GLOO_HIP_MAX_SRCS) return false;
+  const Step &s = steps[i], &w = steps[i + 1], &r = steps[i + 2];
+  return s.kind == GLOO_HIP_STEP_LOCAL_REDUCE && !(s.flags & GLOO_HIP_FROM_INPUTS) && s.length > 0 &&
+         w.kind == GLOO_HIP_STEP_WAIT_RECV && r.kind == GLOO_HIP_STEP_REDUCE &&
+         r.flags == GLOO_HIP_SRC_ARENA && r.dst_off == s.dst_off && r.length == s.length;
+}
+// COPY(inbox -> output 0, R) directly followed by a LOCAL_BCAST whose range
+// holds R.
+bool broadcastsReceive(const std::vector<Step>& steps, size_t i, size_t nptrs) {
+  if (i + 1 >= steps.size() || nptrs < 2) return false;
+  const Step &c = steps[i], &b = steps[i + 1];
+  return c.kind == GLOO_HIP_STEP_COPY && c.flags == GLOO_HIP_SRC_ARENA && c.length > 0 &&
+         b.kind == GLOO_HIP_STEP_LOCAL_BCAST && b.dst_off <= c.dst_off &&
+         c.dst_off + c.length <= b.dst_off + b.length;
+}
+}  // namespace
+
 void markInterpBatches(InterpStep* v, size_t n, size_t es) {
   using Range = std::pair<const char*, const char*>;
   auto touch = [&](const InterpStep& t, std::vector<Range>* rd, std::vector<Range>* wr) {
@@ -77,6 +111,8 @@ void markInterpBatches(InterpStep* v, size_t n, size_t es) {
       for (int j = 0; j < t.nsrc; j++) rd->push_back({t.src[j], t.src[j] + bytes});
       wr->push_back({t.dst, t.dst + bytes});
     }
+    if (t.kind == kInterpCopy)  // a multi-destination copy writes them all
+      for (int j = 0; j < t.nxdst; j++) wr->push_back({t.xdst[j], t.xdst[j] + bytes});
   };
   auto meet = [](const std::vector<Range>& x, const std::vector<Range>& y) {
     for (const Range& a : x)
@@ -479,12 +515,74 @@ void PlanExecutor::buildInterp() {
   };
   const std::vector<size_t> cuts = slices_ > 1 ? userCuts(plan_) : std::vector<size_t>();
   auto pieces = [&](const Step& t) { return cutRange(cuts, t.dst_off, t.length); };
+  // Output 0's elements [off, +len) (or, with `from`, the bytes at `from`,
+  // which then also go to output 0) to every other output: multi-destination
+  // copies that load each tile once, 1 + kMaxCopyEntries destinations a step.
+  auto bcast = [&](size_t off, size_t len, const char* from) {
+    const size_t bytes = len * es_;
+    size_t j = from ? 0 : 1;
+    const char* src = from ? from : userPtr(0) + off * es_;
+    while (j < ptrs_.size()) {
+      const size_t before = v.size();
+      if (!copy((j == 0 ? userPtr(0) : outPtr(j)) + off * es_, src, len)) return false;
+      j++;
+      if (v.size() == before) continue;  // nothing to move, or this output is the source itself
+      for (; j < ptrs_.size() && v.back().nxdst < kMaxCopyEntries; j++) {
+        char* d = outPtr(j) + off * es_;
+        if (d == src) continue;
+        if (d < src + bytes && src < d + bytes) return false;
+        v.back().xdst[v.back().nxdst++] = d;
+      }
+      src = userPtr(0) + off * es_;  // further groups re-read the local copy
+    }
+    return true;
+  };
+  // the pipelined halving-doubling's step pairs that run as one pass (enqueue())
+  const bool fuseLocal = planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED && !custom_ && !anyRemote_;
   std::vector<const char*> foldSrcs;
   const std::vector<Step>& steps = plan_.steps;
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     const size_t bytes = s.length * es_;
     if (bytes > limit) return fail();
+    // LOCAL_REDUCE(R), WAIT_RECV, REDUCE(R <- inbox): the wait, then ONE left
+    // fold of the pointers and the inbox region, the reference's
+    // ((p0 op p1) ... op p(k-1)) op inbox.  (Sliced: only when R is one piece.)
+    if (fuseLocal && s.kind == GLOO_HIP_STEP_LOCAL_REDUCE && foldsWithReceive(steps, i, ptrs_.size()) &&
+        pieces(s).size() == 1) {
+      const Step& rd = steps[i + 2];
+      withSeq(push(kInterpWait), i + 1, waitFlag(steps[i + 1].peer, steps[i + 1].slot));
+      std::vector<const char*> srcs;
+      for (size_t j = 0; j < ptrs_.size(); j++) srcs.push_back(outPtr(j) + s.dst_off * es_);
+      srcs.push_back(arenaAt(rd.src_off, rd.length));
+      fold(userPtr(0) + s.dst_off * es_, srcs, s.length, 0);
+      i += 2;
+      continue;
+    }
+    // COPY(inbox -> output 0, R) + LOCAL_BCAST over a range holding R: the
+    // inbox is read once and stored to every output; the rest of the
+    // broadcast range (already local) stays a broadcast from output 0.
+    if (fuseLocal && s.kind == GLOO_HIP_STEP_COPY && broadcastsReceive(steps, i, ptrs_.size())) {
+      const Step& bc = steps[i + 1];
+      if (bc.length * es_ > limit) return fail();
+      std::vector<size_t> c2 = cuts;
+      c2.push_back(s.dst_off);
+      c2.push_back(s.dst_off + s.length);
+      std::sort(c2.begin(), c2.end());
+      const auto pcs = cutRange(c2, bc.dst_off, bc.length);
+      bool whole = false;  // sliced: R must stay one step (slice g of a message belongs to workgroup g)
+      for (const auto& pc : pcs) whole = whole || (pc.first == s.dst_off && pc.second == s.length);
+      if (whole) {
+        bool ok = true;
+        for (const auto& pc : pcs)
+          ok = ok && bcast(pc.first, pc.second,
+                           pc.first == s.dst_off && pc.second == s.length ? arenaAt(s.src_off, s.length) : nullptr);
+        if (!ok) return fail();
+        if (v.size() > (size_t)kInterpMaxSteps) return fail();
+        i += 1;
+        continue;
+      }
+    }
     switch (s.kind) {
       case GLOO_HIP_STEP_DECL_RECV:
       case GLOO_HIP_STEP_WAIT_SEND:
@@ -540,8 +638,7 @@ void PlanExecutor::buildInterp() {
         break;
       case GLOO_HIP_STEP_LOCAL_BCAST:
         for (const auto& pc : pieces(s))
-          for (size_t j = 1; j < ptrs_.size(); j++)
-            if (!copy(outPtr(j) + pc.first * es_, userPtr(0) + pc.first * es_, pc.second)) return fail();
+          if (!bcast(pc.first, pc.second, nullptr)) return fail();
         break;
       case GLOO_HIP_STEP_FOLD_SRC:
         foldSrcs.push_back(sendSrc(s));
@@ -557,6 +654,7 @@ void PlanExecutor::buildInterp() {
     }
     if (v.size() > (size_t)kInterpMaxSteps) return fail();
   }
+  if (v.size() > (size_t)kInterpMaxSteps) return fail();
   if (v.empty()) return;
   // Batches (signal.h kInterpDefer): a run of waits polls every flag before
   // its one acquire and barrier, and a run of mutually independent data steps
@@ -642,8 +740,98 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
     auto it = stampSlotOf_.find(step);
     return it == stampSlotOf_.end() ? nullptr : stamps_ + (size_t)kStampSlotWords * it->second;
   };
+  // Output 0's elements [off, +len) to outputs first.. in ONE pass that reads
+  // it once: a one-source fold into output `first` that forwards each tile to
+  // the outputs after it (launchFoldSend; no flags), or the local copy kernel
+  // for a single destination.  (k - 1 copies read it k - 1 times: HD with 4
+  // pointers of 64 MiB per rank spent 65 % of its time in the local passes,
+  // profiles/round6/r6f/multi_pointer_p2.jsonl.)  `from`: the bytes come from
+  // there instead (an inbox region) and output 0 is the first destination.
+  auto broadcast = [&](size_t offElems, size_t lenElems, const char* from) {
+    const size_t off = offElems * es_, bytes = lenElems * es_;
+    const void* src0 = from ? from : userPtr(0) + off;
+    for (size_t j0 = from ? 0 : 1; j0 < ptrs_.size(); j0 += 1 + kMaxCopyEntries) {
+      const size_t j1 = std::min(ptrs_.size(), j0 + 1 + kMaxCopyEntries);
+      if (j1 - j0 == 1) {
+        const CopyDesc d{userPtr(j0) + off, src0, bytes, nullptr, Seq{}, nullptr,
+                         copySignalGrid(bytes, kCopyOutBlocks)};
+        checkRc(launchCopySignalMulti(&d, 1, epoch, stream_, kCopyStorePlain), "copy kernel (broadcast)");
+      } else {
+        FwdDesc fwd[kMaxCopyEntries];
+        int nf = 0;
+        for (size_t j = j0 + 1; j < j1; j++) fwd[nf++] = FwdDesc{userPtr(j) + off, nullptr, Seq{}};
+        checkRc(launchFoldSend(op_, dtype_, userPtr(j0) + off, &src0, 1, lenElems, 0, fwd, nf, nullptr, epoch,
+                               stream_),
+                "broadcast (one-source fold + forwards)");
+      }
+      src0 = userPtr(0) + off;  // further groups re-read the local copy
+    }
+  };
+  // The per-range local steps of the pipelined halving-doubling run in one
+  // pass with their neighbour (below); custom ops, event profiling and
+  // pointers on other GPUs of the process keep the plan's own steps.
+  const bool fuseLocal = planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED && deviceSignal_ && !custom_ &&
+                         !profiling_ && !anyRemote_;
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
+    // Local fold + first send: LOCAL_REDUCE(R) then SEND(R) is one fold of
+    // the k pointers that stores each tile to output 0 and into the peer's
+    // inbox, its last workgroup publishing the arrival (fold + forward).
+    // More than GLOO_HIP_MAX_SRCS pointers: chained folds, the last carries
+    // the forward.
+    if (fuseLocal && foldsIntoSend(steps, i)) {
+      const Step& t = steps[i + 1];
+      const size_t off = s.dst_off * es_;
+      char* out0 = userPtr(0) + off;
+      std::vector<const void*> srcs;
+      size_t j = 0;
+      for (; j < ptrs_.size() && srcs.size() < GLOO_HIP_MAX_SRCS; j++) srcs.push_back(userPtr(j) + off);
+      while (j < ptrs_.size()) {
+        checkRc(gloo_hip_reduce_multi(op_, dtype_, out0, srcs.data(), (int)srcs.size(), s.length, stream_),
+                "gloo_hip_reduce_multi");
+        srcs.assign(1, out0);
+        for (; j < ptrs_.size() && srcs.size() < GLOO_HIP_MAX_SRCS; j++) srcs.push_back(userPtr(j) + off);
+      }
+      const FwdDesc fwd{sendDst(t), sigFlag(t.peer, t.slot), seqOf(i + 1, r, graph)};
+      checkRc(launchFoldSend(op_, dtype_, out0, srcs.data(), (int)srcs.size(), s.length, 0, &fwd, 1,
+                             ticket_ + (size_t)t.peer * GLOO_HIP_NUM_SLOTS + t.slot, epoch, stream_),
+              "local fold + send");
+      foldSendUsed_ = true;
+      i += 1;
+      continue;
+    }
+    // Local fold + first receive-reduce: LOCAL_REDUCE(R), WAIT_RECV,
+    // REDUCE(R <- inbox) is the wait, then ONE left fold with the k pointers
+    // first and the inbox region last: ((p0 op p1) ... op p(k-1)) op inbox,
+    // the reference's association and operand order.  The wait stays a
+    // kernel of its own: a grid that spins while it holds the GPU could
+    // starve the sender where ranks share one.
+    if (fuseLocal && foldsWithReceive(steps, i, ptrs_.size())) {
+      const Step &w = steps[i + 1], &rd = steps[i + 2];
+      GLOO_AMD_HIP_CHECK(launchWait(waitFlag(w.peer, w.slot), seqOf(i + 1, r, graph), epoch, timeoutTicks,
+                                    ctx_->errorWordDevicePtr(me), stream_));
+      const size_t off = s.dst_off * es_;
+      std::vector<const void*> srcs;
+      for (size_t j = 0; j < ptrs_.size(); j++) srcs.push_back(userPtr(j) + off);
+      srcs.push_back(arenaAt(rd.src_off, rd.length));
+      StampScope stamp(slotOf(i + 2));
+      checkRc(gloo_hip_reduce_multi(op_, dtype_, userPtr(0) + off, srcs.data(), (int)srcs.size(), s.length, stream_),
+              "local fold + receive-reduce");
+      i += 2;
+      continue;
+    }
+    // Receive + broadcast: COPY(inbox -> output 0, R) then a LOCAL_BCAST
+    // holding R reads the inbox once and stores to every output; what the
+    // broadcast covers besides R is already local and goes out from output 0.
+    if (fuseLocal && broadcastsReceive(steps, i, ptrs_.size())) {
+      const Step& bc = steps[i + 1];
+      broadcast(s.dst_off, s.length, arenaAt(s.src_off, s.length));
+      if (bc.dst_off < s.dst_off) broadcast(bc.dst_off, s.dst_off - bc.dst_off, nullptr);
+      const size_t end = s.dst_off + s.length, bend = bc.dst_off + bc.length;
+      if (end < bend) broadcast(end, bend - end, nullptr);
+      i += 1;
+      continue;
+    }
     // A run of consecutive SENDs (a mesh schedule's sends to every peer):
     // all in flight at once.
     if (s.kind == GLOO_HIP_STEP_SEND && i + 1 < steps.size() && steps[i + 1].kind == GLOO_HIP_STEP_SEND) {
@@ -745,9 +933,12 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
     if (fuse) {
       const bool isWait = s.kind == GLOO_HIP_STEP_WAIT_RECV || s.kind == GLOO_HIP_STEP_WAIT_NOTIFY;
       const Step* t = isWait && i + 1 < steps.size() ? &steps[i + 1] : &s;
-      // (a three-operand REDUCE, out = in op inbox, is not a fused shape)
+      // (a three-operand REDUCE, out = in op inbox, is not a fused shape; a
+      // COPY that the receive + broadcast pass above takes stays with it)
       const bool body = (t->kind == GLOO_HIP_STEP_REDUCE && !(t->flags & GLOO_HIP_FROM_INPUTS)) ||
-                        t->kind == GLOO_HIP_STEP_COPY || t->kind == GLOO_HIP_STEP_SEND;
+                        (t->kind == GLOO_HIP_STEP_COPY &&
+                         !(fuseLocal && isWait && broadcastsReceive(steps, i + 1, ptrs_.size()))) ||
+                        t->kind == GLOO_HIP_STEP_SEND;
       if (body && t->length * es_ <= kFuseBytes && (isWait || t->kind == GLOO_HIP_STEP_SEND)) {
         int op = 0;
         char* dst = nullptr;
@@ -978,32 +1169,12 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
         break;
       }
       case GLOO_HIP_STEP_LOCAL_BCAST: {
-        // Output 0 to every other output in ONE pass that reads it once: a
-        // one-source fold into output 1 that forwards each tile to outputs
-        // 2.. (launchFoldSend; no flags), or the local copy kernel for a
-        // single destination.  (k - 1 copies read it k - 1 times: HD with 4
-        // pointers of 64 MiB per rank spent 65 % of its time in the local
-        // passes, profiles/round6/r6f/multi_pointer_p2.jsonl.)  Outputs on
-        // other GPUs of the process keep the peer copies.
+        // Output 0 to every other output in one pass (broadcast above).
+        // Outputs on other GPUs of the process keep the peer copies.
         const size_t off = s.dst_off * es_, bytes = s.length * es_;
         if (bytes == 0 || ptrs_.size() < 2) break;
         if (!anyRemote_ && !custom_) {
-          const void* src0 = userPtr(0) + off;
-          for (size_t j0 = 1; j0 < ptrs_.size(); j0 += 1 + kMaxCopyEntries) {
-            const size_t j1 = std::min(ptrs_.size(), j0 + 1 + kMaxCopyEntries);
-            if (j1 - j0 == 1) {
-              const CopyDesc d{userPtr(j0) + off, src0, bytes, nullptr, Seq{}, nullptr,
-                               copySignalGrid(bytes, kCopyOutBlocks)};
-              checkRc(launchCopySignalMulti(&d, 1, epoch, stream_, kCopyStorePlain), "copy kernel (broadcast)");
-              continue;
-            }
-            FwdDesc fwd[kMaxCopyEntries];
-            int nf = 0;
-            for (size_t j = j0 + 1; j < j1; j++) fwd[nf++] = FwdDesc{userPtr(j) + off, nullptr, Seq{}};
-            checkRc(launchFoldSend(op_, dtype_, userPtr(j0) + off, &src0, 1, s.length, 0, fwd, nf, nullptr, epoch,
-                                   stream_),
-                    "broadcast (one-source fold + forwards)");
-          }
+          broadcast(s.dst_off, s.length, nullptr);
           break;
         }
         for (size_t j = 1; j < ptrs_.size(); j++)

@@ -27,6 +27,9 @@
 
 namespace gloo_amd {
 
+// plan.h: where gloo_hip_plan* report why a plan was refused.
+void (*planErrorSink)(int code, const char* msg) = nullptr;
+
 namespace {
 
 Step mk(int kind, int peer = -1, int slot = 0, int flags = 0, uint64_t dst = 0, uint64_t src = 0,
@@ -396,18 +399,31 @@ Plan planRingChunkedMesh(int rank, int size, uint64_t count, int nptrs) {
 // ---------------------------------------------------------------------------
 // AllreduceHalvingDoubling (gloo/allreduce_halving_doubling.h:67-362), GPU
 // twin gloo/cuda_allreduce_halving_doubling.cc:246-410.
+//
+// pipelined: the GPU twin's pipelineBroadcastAndReduce (pipelined_, :246-455).
+// The exchange is the same; only the local multi-pointer steps move.  The
+// whole-range LOCAL_REDUCE becomes one over the first send's range before
+// that send (reduceBeforeFirstSend_, :253-254) and one over the first
+// receive's range before its wait (reduceBeforeFirstRecv_, :274-280); the two
+// ranges are the halves of the padded buffer, so together they cover [0, n).
+// The whole-range LOCAL_BCAST becomes one per all-gather step over the range
+// of devicePointerInit (:416-437), after the step's copy and before its
+// notification (:376-383).  The reference keeps the whole-range steps for one
+// rank and for a rank in a binary block of one (:477-479, :520-522, :537);
+// with one pointer there are no local steps at all.
 // ---------------------------------------------------------------------------
-Plan planHalvingDoubling(int rank, int size, uint64_t count, int nptrs) {
+Plan planHalvingDoubling(int rank, int size, uint64_t count, int nptrs, bool pipelined) {
   Plan p;
   if (count == 0) return p;                                             // run() :226-228
-  if (nptrs > 1) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_REDUCE, -1, 0, 0, 0, 0, count));
+  const Blocks bl = binaryBlocks(rank, size);                           // :102
+  const uint32_t swb = bl.stepsWithinBlock;
+  const bool pipe = pipelined && nptrs > 1 && size > 1 && swb > 0;
+  if (nptrs > 1 && !pipe) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_REDUCE, -1, 0, 0, 0, 0, count));
   if (size == 1) {
     if (nptrs > 1) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_BCAST, -1, 0, 0, 0, 0, count));
     return p;
   }
-  const Blocks bl = binaryBlocks(rank, size);                           // :102
   HDGeometry g = hdGeometry(rank, size, count, bl);                     // :107-157
-  const uint32_t swb = bl.stepsWithinBlock;
   p.arena = g.chunkSize << g.steps;                                     // recvBuf_ (:80)
   for (uint32_t i = 0; i < swb; i++)
     p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, g.dest[i], GLOO_HIP_SLOT_DATA0, 0, g.regionOff[i],
@@ -450,10 +466,14 @@ Plan planHalvingDoubling(int rank, int size, uint64_t count, int nptrs) {
   // run() :225-362
   uint64_t bufferOffset = 0;
   uint64_t numItems = swb > 0 ? g.chunkSize << (g.steps - 1) : count;
+  if (pipe && g.sendOffsets[0] < count)                                 // reduceBeforeFirstSend_
+    p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_REDUCE, -1, 0, 0, g.sendOffsets[0], 0, g.sendCounts[0]));
   for (uint32_t i = 0; i < swb; i++) {                                  // :244-259
     if (g.sendOffsets[i] < count)
       p.steps.push_back(mk(GLOO_HIP_STEP_SEND, g.dest[i], GLOO_HIP_SLOT_DATA0, 0, 0, g.sendOffsets[i],
                            g.sendCounts[i]));
+    if (pipe && i == 0 && g.recvOffsets[0] < count)                     // reduceBeforeFirstRecv_
+      p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_REDUCE, -1, 0, 0, g.recvOffsets[0], 0, g.recvCounts[0]));
     if (g.recvOffsets[i] < count) {
       p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, g.dest[i], GLOO_HIP_SLOT_DATA0));
       p.steps.push_back(mk(GLOO_HIP_STEP_REDUCE, -1, 0, GLOO_HIP_SRC_ARENA, g.recvOffsets[i],
@@ -502,10 +522,22 @@ Plan planHalvingDoubling(int rank, int size, uint64_t count, int nptrs) {
       p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, g.sendOffsets[i],
                            bufferOffset, g.sendCounts[i]));
     }
+    if (pipe) {                                                         // broadcastOps_[i], :416-437
+      // the first broadcast takes this rank's own reduce-scatter result with
+      // the first chunk received; a range starting past the end is skipped
+      // (offset > count_, :424) and one clipped to nothing moves nothing
+      const bool last = i == (int)swb - 1;
+      const uint64_t off = last ? std::min(g.recvOffsets[i], g.sendOffsets[i]) : g.sendOffsets[i];
+      uint64_t len = last ? g.recvCounts[i] + g.sendCounts[i] : g.sendCounts[i];
+      if (off <= count) {
+        len = std::min(len, count - off);
+        if (len > 0) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_BCAST, -1, 0, 0, off, 0, len));
+      }
+    }
     numItems <<= 1;
     p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, g.dest[i], GLOO_HIP_SLOT_NOTIFY));
   }
-  if (nptrs > 1) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_BCAST, -1, 0, 0, 0, 0, count));  // :349-352
+  if (nptrs > 1 && !pipe) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_BCAST, -1, 0, 0, 0, 0, count));  // :349-352
   for (int i = (int)swb - 1; i >= 0; i--)                               // :357-359
     p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, g.dest[i], GLOO_HIP_SLOT_NOTIFY));
   if (sentToSmallerBlock)                                               // :364-366
@@ -1201,6 +1233,11 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
   if (nptrs < 1) throw std::invalid_argument("need at least one pointer");
   if (algo & GLOO_HIP_ALGO_MESH) {
     const int base = algo & ~GLOO_HIP_ALGO_MESH;
+    // an order of the reference's own route: a mesh plan has no first send
+    // or all-gather step to pipeline the local passes with
+    if (base == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED)
+      throw std::invalid_argument(
+          "pipelined halving-doubling has no mesh form (GLOO_HIP_ALGO_MESH): it is an order of the reference's route");
     if (base == GLOO_HIP_ALGO_REDUCE_SCATTER && (int)recvElems.size() != size)
       throw std::invalid_argument("recvElems must have size entries");
     return makeMeshPlan(base, rank, size, count, nptrs, recvElems);
@@ -1209,7 +1246,8 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
     case GLOO_HIP_ALGO_RING_CHUNKED: return planRingChunked(rank, size, count, nptrs);
     case GLOO_HIP_ALGO_RING_CHUNKED_MESH: return planRingChunkedMesh(rank, size, count, nptrs);
     case GLOO_HIP_ALGO_RING_CHUNKED_PIPE: return planRingChunkedPipe(rank, size, count, nptrs);
-    case GLOO_HIP_ALGO_HALVING_DOUBLING: return planHalvingDoubling(rank, size, count, nptrs);
+    case GLOO_HIP_ALGO_HALVING_DOUBLING: return planHalvingDoubling(rank, size, count, nptrs, false);
+    case GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED: return planHalvingDoubling(rank, size, count, nptrs, true);
     case GLOO_HIP_ALGO_RING: return planRing(rank, size, count, nptrs);
     case GLOO_HIP_ALGO_LOCAL: return planLocal(rank, size, count, nptrs);
     case GLOO_HIP_ALGO_BCUBE: return planBcube(rank, size, count, nptrs, recvElems.empty() ? 2 : recvElems[0]);
@@ -1260,7 +1298,8 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
       if (!p.steps.empty()) std::memcpy(steps, p.steps.data(), p.steps.size() * sizeof(gloo_hip_step_t));
     }
     return GLOO_HIP_OK;
-  } catch (const std::exception&) {
+  } catch (const std::exception& e) {
+    if (gloo_amd::planErrorSink) gloo_amd::planErrorSink(GLOO_HIP_EINVAL_ARG, e.what());
     return GLOO_HIP_EINVAL_ARG;
   }
 }

@@ -722,14 +722,22 @@ __device__ __forceinline__ void wt_byte(char* p, char v) {
 
 // WT: every byte of dst is stored write-through (an interpreter SEND under
 // the once-per-launch protocol, fwdLean: its flag then needs no release).
+// nx further destinations xd[r] (a local multi-destination step, signal.h
+// InterpStep::xdst) receive the same bytes with plain stores: the head and
+// tail byte-wise, each body packet as a 16-byte store at that destination's
+// own misalignment (descriptor at its aligned-down address, the byte offset
+// in soffset, as a misaligned source's and fold_send_kernel's forwards).
 template <bool WT = false>
-__device__ __forceinline__ void interp_copy(char* dst, const char* src, uint64_t n) {
+__device__ __forceinline__ void interp_copy(char* dst, const char* src, uint64_t n, int nx = 0,
+                                            char* const* xd = nullptr, uint64_t xoff = 0) {
   const uint64_t t = threadIdx.x;
   uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
   if (head > n) head = n;
   if (t < head) {
-    if (WT) wt_byte(dst + t, src[t]);
-    else dst[t] = src[t];
+    const char c = src[t];
+    if (WT) wt_byte(dst + t, c);
+    else dst[t] = c;
+    for (int r = 0; r < nx; r++) xd[r][xoff + t] = c;
   }
   const uint64_t body = (n - head) / 16 * 16;
   char* d = dst + head;
@@ -745,10 +753,18 @@ __device__ __forceinline__ void interp_copy(char* dst, const char* src, uint64_t
     for (int u = 0; u < kInterpCopyUnroll; u++) v[u] = bload<0>(rs, lane_off + u * kInterpBlock * 16, ss.mis);
 #pragma unroll
     for (int u = 0; u < kInterpCopyUnroll; u++) bstore<WT ? kAuxWT : 0>(rd, lane_off + u * kInterpBlock * 16, v[u]);
+    for (int r = 0; r < nx; r++) {
+      const Src xr = src_of(xd[r] + xoff + head);
+      const auto rx = make_rsrc(xr.base + b, bytes + xr.mis);
+#pragma unroll
+      for (int u = 0; u < kInterpCopyUnroll; u++) bstore<0>(rx, lane_off + u * kInterpBlock * 16, v[u], xr.mis);
+    }
   }
   for (uint64_t i = head + body + t; i < n; i += kInterpBlock) {
-    if (WT) wt_byte(dst + i, src[i]);
-    else dst[i] = src[i];
+    const char c = src[i];
+    if (WT) wt_byte(dst + i, c);
+    else dst[i] = c;
+    for (int r = 0; r < nx; r++) xd[r][xoff + i] = c;
   }
 }
 
@@ -876,8 +892,9 @@ __global__ __launch_bounds__(kInterpBlock) void plan_interp_kernel(const InterpS
     const uint64_t hi = lo + q < n ? lo + q : n;
     if (kind == kInterpSend) {
       interp_copy<true>(st.dst + lo * sizeof(S), st.src[0] + lo * sizeof(S), (hi - lo) * sizeof(S));
-    } else if (kind == kInterpCopy || kind == kInterpSend) {
-      interp_copy(st.dst + lo * sizeof(S), st.src[0] + lo * sizeof(S), (hi - lo) * sizeof(S));
+    } else if (kind == kInterpCopy) {
+      interp_copy(st.dst + lo * sizeof(S), st.src[0] + lo * sizeof(S), (hi - lo) * sizeof(S), st.nxdst, st.xdst,
+                  lo * sizeof(S));
     } else if (kind == kInterpFold) {
       interp_fold<Tr, OP>(st, lo, hi);
     }

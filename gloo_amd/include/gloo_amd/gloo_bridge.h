@@ -248,8 +248,8 @@ class HipPlanAlgorithm : public Algorithm {
  public:
   HipPlanAlgorithm(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, int count,
                    const std::vector<int>& recvElems, const std::vector<hipStream_t>& streams,
-                   const ReductionFunction<T>* fn)
-      : Algorithm(context) {
+                   const ReductionFunction<T>* fn, int algo = ALGO /* a run-time variant of ALGO */)
+      : Algorithm(context), algoCode_(algo) {
     GLOO_ENFORCE(!ptrs.empty(), "need at least one pointer");
     // gloo/cuda_allreduce_ring_chunked.cc:55-58
     GLOO_ENFORCE(streams.empty() || streams.size() == ptrs.size(), "one stream per pointer, or none");
@@ -258,7 +258,7 @@ class HipPlanAlgorithm : public Algorithm {
     std::vector<void*> p(ptrs.begin(), ptrs.end());
     std::vector<gloo_hip_stream_t> s(streams.begin(), streams.end());
     hip_bridge::check(
-        gloo_hip_algorithm_create_streams(boot_->handle(), ALGO, op, hip_bridge::DType<T>::value, p.data(),
+        gloo_hip_algorithm_create_streams(boot_->handle(), algo, op, hip_bridge::DType<T>::value, p.data(),
                                           (int)p.size(), (size_t)(count > 0 ? count : 0),
                                           recvElems.empty() ? nullptr : recvElems.data(),
                                           s.empty() ? nullptr : s.data(), (int)s.size(), W::kind, &algo_),
@@ -270,8 +270,11 @@ class HipPlanAlgorithm : public Algorithm {
   }
 
   void run() override { hip_bridge::check(gloo_hip_algorithm_run(algo_), "run"); }
+  // The gloo_hip_algo_t the constructor selected.
+  int algorithm() const { return algoCode_; }
 
  protected:
+  int algoCode_;
   std::unique_ptr<hip_bridge::BootstrapContext> boot_;
   gloo_hip_algorithm_t algo_ = nullptr;
 };
@@ -289,16 +292,19 @@ template <typename T, typename W = HipDeviceWorkspace<T>>
 class HipAllreduceHalvingDoubling : public HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W> {
  public:
   // pipelineBroadcastAndReduce (gloo/cuda_allreduce_halving_doubling.h:29)
-  // overlaps the reference's per-chunk local reduce / broadcast with the
-  // exchange; here a rank's pointers are folded in one fused pass before the
-  // exchange and broadcast in one pass after it, so the flag changes no
-  // result and is accepted for source compatibility (DESIGN.md §8 round 6,
-  // "Multi-pointer local passes").
+  // = true selects GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED: the same
+  // exchange and result bytes, with the local fold of a rank's pointers cut
+  // into the first send's and the first receive's range and each range
+  // broadcast to the other pointers as the all-gather delivers it
+  // (DESIGN.md §7).  That order stays on the reference's route at every
+  // size; false keeps the default, which runs as the mesh plan at 2-8 ranks.
   HipAllreduceHalvingDoubling(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, const int count,
                               const std::vector<hipStream_t>& streams = std::vector<hipStream_t>(),
-                              bool /*pipelineBroadcastAndReduce*/ = false,
+                              bool pipelineBroadcastAndReduce = false,
                               const ReductionFunction<T>* fn = ReductionFunction<T>::sum)
-      : HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W>(context, ptrs, count, {}, streams, fn) {}
+      : HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W>(
+            context, ptrs, count, {}, streams, fn,
+            pipelineBroadcastAndReduce ? GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED : GLOO_HIP_ALGO_HALVING_DOUBLING) {}
 };
 
 // gloo::CudaAllreduceHalvingDoublingPipelined

@@ -117,12 +117,12 @@ class HipPlanAlgorithm : public Algorithm {
  public:
   HipPlanAlgorithm(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, int count,
                    const std::vector<int>& recvElems, const std::vector<hipStream_t>& streams,
-                   const HipReductionFunction<T>* fn)
+                   const HipReductionFunction<T>* fn, int algo = ALGO /* a run-time variant of ALGO */)
       : Algorithm(context) {
     // one stream per pointer, or none (gloo/cuda_allreduce_ring_chunked.cc:55-58)
     GLOO_AMD_ENFORCE(streams.empty() || streams.size() == ptrs.size(), "one stream per pointer, or none");
     std::vector<void*> p(ptrs.begin(), ptrs.end());
-    exec_ = PlanExecutor::create(context, ALGO, fn->type(), DType<T>::value, p,
+    exec_ = PlanExecutor::create(context, algo, fn->type(), DType<T>::value, p,
                                            static_cast<size_t>(count), recvElems,
                                            streams.empty() ? nullptr : streams[0], std::vector<void*>{}, 0,
                                            W::kind);
@@ -151,16 +151,19 @@ class HipAllreduceHalvingDoubling : public HipPlanAlgorithm<T, GLOO_HIP_ALGO_HAL
                               const HipReductionFunction<T>* fn = HipReductionFunction<T>::sum)
       : HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W>(context, ptrs, count, {}, streams, fn) {}
   // The reference's exact signature (gloo/cuda_allreduce_halving_doubling.h:25-30).
-  // pipelineBroadcastAndReduce overlaps the reference's per-chunk local
-  // reduce / broadcast LocalOps with the exchange; here the local fold of a
-  // rank's pointers is one fused pass before the exchange and the broadcast
-  // one pass after it (output 0 read once), so the flag changes no result
-  // and is accepted for source compatibility (what the overlap could hide:
-  // DESIGN.md §8 round 6, "Multi-pointer local passes").
+  // pipelineBroadcastAndReduce = true selects
+  // GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED: the same exchange and result
+  // bytes, with the local fold of a rank's pointers cut into the first send's
+  // and the first receive's range (each in one pass with that send / that
+  // receive's reduction) and each range broadcast to the other pointers in
+  // the pass that takes it out of its inbox.  That order stays
+  // on the reference's route at every size; false keeps the default, which
+  // runs as the mesh plan at 2-8 ranks.
   HipAllreduceHalvingDoubling(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, int count,
-                              const std::vector<hipStream_t>& streams, bool /*pipelineBroadcastAndReduce*/)
-      : HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W>(context, ptrs, count, {}, streams,
-                                                               HipReductionFunction<T>::sum) {}
+                              const std::vector<hipStream_t>& streams, bool pipelineBroadcastAndReduce)
+      : HipPlanAlgorithm<T, GLOO_HIP_ALGO_HALVING_DOUBLING, W>(
+            context, ptrs, count, {}, streams, HipReductionFunction<T>::sum,
+            pipelineBroadcastAndReduce ? GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED : GLOO_HIP_ALGO_HALVING_DOUBLING) {}
 };
 
 template <typename T, typename W = HipDeviceWorkspace<T>>
@@ -205,7 +208,8 @@ class HipAllreduceBcube : public HipPlanAlgorithm<T, GLOO_HIP_ALGO_BCUBE, W> {
 
 // CudaAllreduceHalvingDoublingPipelined
 // (gloo/cuda_allreduce_halving_doubling_pipelined.h:13-28): halving-doubling
-// with pipelineBroadcastAndReduce set (see HipAllreduceHalvingDoubling).
+// with pipelineBroadcastAndReduce set (GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED,
+// see HipAllreduceHalvingDoubling).
 template <typename T, typename W = HipDeviceWorkspace<T>>
 class HipAllreduceHalvingDoublingPipelined : public HipAllreduceHalvingDoubling<T, W> {
  public:

@@ -30,6 +30,12 @@ struct NewStyleOptions {
 // algo: GLOO_HIP_ALGO_ALLREDUCE_RING, GLOO_HIP_ALGO_ALLREDUCE_BCUBE or
 // GLOO_HIP_ALGO_REDUCE, optionally | GLOO_HIP_ALGO_MESH (mesh.h).
 Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewStyleOptions& o);
+// Receives the text of a planner's refusal (an unknown algorithm, a mesh form
+// that does not exist, bad sizes) when gloo_hip_plan / gloo_hip_plan_ex return
+// GLOO_HIP_EINVAL_ARG.  The library installs its last-error text here
+// (errors.cc); a host-only build of the planners alone leaves it null.
+extern void (*planErrorSink)(int code, const char* msg);
+
 inline bool isNewStyle(int algo) {
   algo &= ~GLOO_HIP_ALGO_MESH;
   return algo == GLOO_HIP_ALGO_ALLREDUCE_RING || algo == GLOO_HIP_ALGO_ALLREDUCE_BCUBE ||

@@ -119,6 +119,14 @@ struct InterpStep {
   char* dst;
   const char* src[8]; // COPY / SEND: src[0]; FOLD: the sources in order
   uint64_t n;         // elements
+  // COPY: further local destinations of the same bytes (a broadcast to a
+  // rank's other pointers).  Each tile is loaded once and stored to dst and
+  // to every xdst[r], each at its own 16-byte misalignment,
+  // with plain stores (the next reader is the caller, as after the eager
+  // broadcast's local copies above).
+  int32_t nxdst;
+  int32_t pad_;
+  char* xdst[kMaxCopyEntries];
 };
 constexpr int kInterpMaxSteps = 512;
 // InterpStep.flags: this step and the next form one batch.  A WAIT then only
@@ -132,7 +140,8 @@ constexpr int kInterpDefer = 1;
 // Sets kInterpDefer on v[0..n) (executor.cc): step i is deferred when step
 // i+1 is of the same class (wait / non-wait) and touches nothing that any
 // step of the open batch (every step since the last non-deferred one) writes,
-// and writes nothing any of them reads.  `es` = bytes per element of `n`.
+// and writes nothing any of them reads (every destination of a
+// multi-destination step counts as written).  `es` = bytes per element of `n`.
 void markInterpBatches(InterpStep* v, size_t n, size_t es);
 // Flag words per (sender, slot) in a device mailbox: one per slice.
 constexpr int kMaxSlices = 256;

@@ -206,6 +206,21 @@ typedef enum {
    * wherever every rank ends with the same expression trees (P a power of
    * the base, counts of about P and more), else on the reference's route. */
   GLOO_HIP_ALGO_BCUBE = 10,
+  /* CudaAllreduceHalvingDoubling with pipelineBroadcastAndReduce = true
+   * (gloo/cuda_allreduce_halving_doubling.cc:246-455, pipelined_): the
+   * halving-doubling exchange unchanged, with the local multi-pointer steps
+   * cut per range.  The first send's range is reduced before it is sent and
+   * the first receive's range while that message is in flight; each range is
+   * broadcast to the other pointers as the all-gather delivers it, with no
+   * whole-range pass at either end.  Identical to HALVING_DOUBLING's plan for
+   * one pointer, one rank, no elements and a rank in a binary block of one.
+   * It is an order of the reference's route: there is no mesh form
+   * (| GLOO_HIP_ALGO_MESH is refused) and the executor never promotes it, so
+   * at 2-8 ranks plain HALVING_DOUBLING (mesh) is the faster choice where
+   * the flag is not wanted.  The executor runs each local step and its
+   * neighbour in one pass (local fold + first send, local fold + first
+   * receive-reduce, receive + broadcast; executor_run.cc). */
+  GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED = 11,
 } gloo_hip_algo_t;
 
 /* algo | GLOO_HIP_ALGO_MESH: the algorithm's result with mesh data movement,
@@ -303,6 +318,18 @@ typedef struct {
   uint64_t bytes;
 } gloo_hip_interp_desc_t;
 int gloo_hip_interp_batches(const gloo_hip_interp_desc_t* steps, int n, int* defer_out);
+/* The same for step lists with multi-destination copies: a copy (kind 0)
+ * may store its bytes to nxdst further local destinations (a broadcast to a
+ * rank's other pointers, one load per tile), every one of which counts as
+ * written by the step.  nxdst is 0 for every other kind. */
+#define GLOO_HIP_MAX_XDSTS 8
+typedef struct {
+  gloo_hip_interp_desc_t step;
+  int32_t nxdst;
+  int32_t reserved; /* 0 */
+  uint64_t xdst[GLOO_HIP_MAX_XDSTS];
+} gloo_hip_interp_desc_ex_t;
+int gloo_hip_interp_batches_ex(const gloo_hip_interp_desc_ex_t* steps, int n, int* defer_out);
 
 /* ------------------------------------------------------------------------
  * Contexts and algorithms (the GPU allreduce / reduce-scatter drop-ins).

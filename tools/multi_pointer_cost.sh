@@ -1,6 +1,7 @@
 #!/bin/bash
 # P processes of tools/multi_pointer_cost.py on GPU 0.  Usage:
-#   tools/multi_pointer_cost.sh P N K ITERS
+#   tools/multi_pointer_cost.sh P N K ITERS [--pipelined [ALTERNATIONS]]
+# (the --pipelined leg: run with GLOO_AMD_MESH=0, see multi_pointer_cost.py)
 set -o pipefail
 here=$(cd "$(dirname "$0")" && pwd)
 d=$(mktemp -d)
