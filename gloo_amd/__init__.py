@@ -22,11 +22,15 @@ LIB_PATH = os.environ.get("GLOO_AMD_LIB") or os.path.join(_HERE, "libgloo_amd.so
 
 
 class ReductionType(enum.IntEnum):
-    """gloo::ReductionType (gloo/algorithm.h:49-57)."""
+    """gloo::ReductionType (gloo/algorithm.h:49-57), extended by the bitwise
+    ops of PyTorch's ReduceOp (BAND / BOR / BXOR; integer dtypes only)."""
     SUM = 1
     PRODUCT = 2
     MAX = 3
     MIN = 4
+    BAND = 5
+    BOR = 6
+    BXOR = 7
 
 
 class DType(enum.IntEnum):
@@ -46,12 +50,13 @@ DTYPE_NAMES = {"i8": DType.I8, "u8": DType.U8, "i32": DType.I32, "u32": DType.U3
                "i64": DType.I64, "u64": DType.U64, "f16": DType.F16, "bf16": DType.BF16,
                "f32": DType.F32, "f64": DType.F64}
 OP_NAMES = {"sum": ReductionType.SUM, "product": ReductionType.PRODUCT,
-            "max": ReductionType.MAX, "min": ReductionType.MIN}
+            "max": ReductionType.MAX, "min": ReductionType.MIN,
+            "band": ReductionType.BAND, "bor": ReductionType.BOR, "bxor": ReductionType.BXOR}
 
 EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
-            "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi")
+            "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported")
 
 
 class GlooHipError(RuntimeError):
@@ -79,6 +84,7 @@ def _load():
     L.gloo_hip_last_error.restype = ctypes.c_char_p
     L.gloo_hip_version.restype = ctypes.c_char_p
     L.gloo_hip_set_variant.argtypes = [ctypes.c_int]
+    L.gloo_hip_op_supported.argtypes = [ctypes.c_int, ctypes.c_int]
     L.gloo_hip_reduce_staged.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, sz, vp, vp, sz, vp]
     L.gloo_hip_register_op.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int)]
     L.gloo_hip_copy_kernel.argtypes = [vp, vp, sz, ctypes.c_uint, vp]
@@ -105,6 +111,12 @@ def _as_dtype(dtype):
 
 def dtype_size(dtype):
     return lib.gloo_hip_dtype_size(_as_dtype(dtype))
+
+
+def op_supported(op, dtype):
+    """gloo_hip_op_supported: do the kernels implement `op` on `dtype`?  (The
+    bitwise ops take the integer dtypes only.)  Never touches the GPU."""
+    return bool(lib.gloo_hip_op_supported(_as_op(op), _as_dtype(dtype)))
 
 
 def version():
@@ -232,6 +244,9 @@ ReductionFunction.sum = ReductionFunction(ReductionType.SUM)
 ReductionFunction.product = ReductionFunction(ReductionType.PRODUCT)
 ReductionFunction.max = ReductionFunction(ReductionType.MAX)
 ReductionFunction.min = ReductionFunction(ReductionType.MIN)
+ReductionFunction.band = ReductionFunction(ReductionType.BAND)
+ReductionFunction.bor = ReductionFunction(ReductionType.BOR)
+ReductionFunction.bxor = ReductionFunction(ReductionType.BXOR)
 
 
 # ---- contexts and algorithms (GPU allreduce / reduce-scatter drop-ins) -----

@@ -121,6 +121,9 @@ int gloo_hip_context_destroy(gloo_hip_context_t ctx) {
 int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int dtype, void* const* ptrs, int nptrs,
                                  size_t count, const int* recv_elems, gloo_hip_stream_t stream, int workspace,
                                  gloo_hip_algorithm_t* out) {
+  // refused on this rank before any exchange: every rank makes the same call
+  // and fails alike, so nobody waits for a peer
+  if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
     std::vector<int> re;
@@ -142,6 +145,7 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
                                       int nptrs, size_t count, const int* recv_elems,
                                       const gloo_hip_stream_t* streams, int nstreams, int workspace,
                                       gloo_hip_algorithm_t* out) {
+  if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
     // gloo/cuda_allreduce_ring_chunked.cc:55-58
@@ -250,6 +254,8 @@ int gloo_hip_algorithm_destroy(gloo_hip_algorithm_t a) {
 }
 
 int gloo_hip_allreduce(gloo_hip_context_t ctx, const gloo_hip_allreduce_options_t* o) {
+  if (o)  // before the elements == 0 shortcut and any exchange, as create_ws
+    if (const int rc = gloo_amd::checkBitwiseDtype(o->op, o->dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && o, "null argument");
     GLOO_AMD_ENFORCE(o->algorithm == 0 || o->algorithm == GLOO_HIP_ALLREDUCE_RING ||
@@ -266,6 +272,8 @@ int gloo_hip_allreduce(gloo_hip_context_t ctx, const gloo_hip_allreduce_options_
 }
 
 int gloo_hip_reduce_to_root(gloo_hip_context_t ctx, const gloo_hip_reduce_options_t* o) {
+  if (o)
+    if (const int rc = gloo_amd::checkBitwiseDtype(o->op, o->dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && o, "null argument");
     if (o->elements == 0) return;  // gloo/reduce.cc:22-24

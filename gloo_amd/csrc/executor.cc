@@ -510,7 +510,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     gloo_hip_custom_fn fn;
     void* user;
     custom_ = customOp(op_, &fn, &user);
-    GLOO_AMD_ENFORCE(custom_ || isBuiltinOp(op_), "unknown op ", op_);
+    GLOO_AMD_ENFORCE(custom_ || isBuiltinOp(op_, dtype_), "unknown op ", op_, " for dtype ", dtype_);
   }
   GLOO_AMD_ENFORCE(!ptrs_.empty(), "need at least one pointer");
   for (void* p : ptrs_) GLOO_AMD_ENFORCE(p != nullptr || count_ == 0, "null device pointer");

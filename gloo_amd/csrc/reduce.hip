@@ -56,12 +56,17 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <typename S, typename U>
 struct IntTraits {
   using Storage = S;
+  static constexpr bool kIntegral = true;  // carries band / bor / bxor (apply<>)
   __device__ static __forceinline__ S sum(S a, S b) { return (S)(U)((U)a + (U)b); }
   __device__ static __forceinline__ S product(S a, S b) {
     return (S)(U)((U)a * (U)b);
   }
   __device__ static __forceinline__ S max(S a, S b) { return (a < b) ? b : a; }
   __device__ static __forceinline__ S min(S a, S b) { return (b < a) ? b : a; }
+  // on the element's bits; int8 promotes to int and truncates to the same bits
+  __device__ static __forceinline__ S band(S a, S b) { return (S)(a & b); }
+  __device__ static __forceinline__ S bor(S a, S b) { return (S)(a | b); }
+  __device__ static __forceinline__ S bxor(S a, S b) { return (S)(a ^ b); }
 };
 
 // uint8 * uint8 promotes to int in C++; 255*255 fits, truncation gives the
@@ -77,6 +82,7 @@ using TrU64 = IntTraits<uint64_t, uint64_t>;
 template <typename S>
 struct FloatTraits {
   using Storage = S;
+  static constexpr bool kIntegral = false;
   __device__ static __forceinline__ S sum(S a, S b) { return a + b; }
   __device__ static __forceinline__ S product(S a, S b) { return a * b; }
   // std::max(a, b) == (a < b) ? b : a ; std::min(a, b) == (b < a) ? b : a.
@@ -102,6 +108,7 @@ using TrF64 = FloatTraits<double>;
 // rare path's condition; they hide under the memory stream.
 struct TrF16 {
   using Storage = uint16_t;
+  static constexpr bool kIntegral = false;
   __device__ static __forceinline__ float widen(uint16_t x) {
     return (float)__builtin_bit_cast(_Float16, x);
   }
@@ -135,6 +142,7 @@ struct TrF16 {
 // and payload: one compare + select restores the reference's bits.
 struct TrBF16 {
   using Storage = uint16_t;
+  static constexpr bool kIntegral = false;
   __device__ static __forceinline__ float widen(uint16_t x) {
     return __builtin_bit_cast(float, (uint32_t)x << 16);
   }
@@ -158,10 +166,39 @@ struct TrBF16 {
 template <class Tr, int OP>
 __device__ __forceinline__ typename Tr::Storage apply(typename Tr::Storage a,
                                                       typename Tr::Storage b) {
+  static_assert(OP >= GLOO_HIP_SUM && OP <= GLOO_HIP_BXOR, "not a built-in op");
+  static_assert(OP <= GLOO_HIP_MIN || Tr::kIntegral, "bitwise ops are defined for the integer traits only");
   if constexpr (OP == GLOO_HIP_SUM) return Tr::sum(a, b);
   else if constexpr (OP == GLOO_HIP_PRODUCT) return Tr::product(a, b);
   else if constexpr (OP == GLOO_HIP_MAX) return Tr::max(a, b);
-  else return Tr::min(a, b);
+  else if constexpr (OP == GLOO_HIP_MIN) return Tr::min(a, b);
+  else if constexpr (OP == GLOO_HIP_BAND) return Tr::band(a, b);
+  else if constexpr (OP == GLOO_HIP_BOR) return Tr::bor(a, b);
+  else return Tr::bxor(a, b);
+}
+
+// The bitwise ops are instantiated for the unsigned integer traits only: their
+// result does not depend on signedness, so the host entries map a signed dtype
+// to its unsigned twin before the dtype switch (bitwiseKernelDtype) and every
+// kernel exists 3 traits x 3 ops times, not 6 x 3.  The floating traits never
+// instantiate them (by_bitwise_op compiles to nothing there).
+template <class Tr>
+constexpr bool kHasBitwise = Tr::kIntegral && std::is_unsigned<typename Tr::Storage>::value;
+template <int OP>
+using OpTag = std::integral_constant<int, OP>;
+// f(OpTag<OP>) for op in BAND / BOR / BXOR on a trait that carries them; else
+// GLOO_HIP_EINVAL_OP with no message set (f itself never returns that code).
+template <class Tr, class F>
+int by_bitwise_op(int op, F&& f) {
+  if constexpr (kHasBitwise<Tr>) {
+    switch (op) {
+      case GLOO_HIP_BAND: return f(OpTag<GLOO_HIP_BAND>{});
+      case GLOO_HIP_BOR: return f(OpTag<GLOO_HIP_BOR>{});
+      case GLOO_HIP_BXOR: return f(OpTag<GLOO_HIP_BXOR>{});
+      default: break;
+    }
+  }
+  return GLOO_HIP_EINVAL_OP;
 }
 
 // Apply the op lane-wise to one 16-byte packet.
@@ -182,7 +219,11 @@ __device__ __forceinline__ u32x4 generic_packet(u32x4 a, u32x4 b) {
 }
 template <class Tr, int OP>
 __device__ __forceinline__ u32x4 apply_packet(u32x4 a, u32x4 b) {
-  return generic_packet<Tr, OP>(a, b);
+  // bitwise: four dword instructions whatever the element width
+  if constexpr (OP == GLOO_HIP_BAND) return a & b;
+  else if constexpr (OP == GLOO_HIP_BOR) return a | b;
+  else if constexpr (OP == GLOO_HIP_BXOR) return a ^ b;
+  else return generic_packet<Tr, OP>(a, b);
 }
 
 // Byte-lane SWAR specialisations: 16 int8/uint8 adds in 4 dword ops each
@@ -676,7 +717,11 @@ int launch_fused(int op, void* dst, const void* src, size_t n, const uint64_t* w
     case GLOO_HIP_PRODUCT: fused_small_kernel<Tr, GLOO_HIP_PRODUCT><<<1, kFusedBlock, 0, s>>>(d, x, n, wf, wt, tt, err, sf, sv, ep); break;
     case GLOO_HIP_MAX: fused_small_kernel<Tr, GLOO_HIP_MAX><<<1, kFusedBlock, 0, s>>>(d, x, n, wf, wt, tt, err, sf, sv, ep); break;
     case GLOO_HIP_MIN: fused_small_kernel<Tr, GLOO_HIP_MIN><<<1, kFusedBlock, 0, s>>>(d, x, n, wf, wt, tt, err, sf, sv, ep); break;
-    default: return GLOO_HIP_EINVAL_OP;
+    default:
+      return by_bitwise_op<Tr>(op, [&](auto o) {
+        fused_small_kernel<Tr, decltype(o)::value><<<1, kFusedBlock, 0, s>>>(d, x, n, wf, wt, tt, err, sf, sv, ep);
+        return GLOO_HIP_OK;
+      });
   }
   return GLOO_HIP_OK;
 }
@@ -941,7 +986,11 @@ int launch_interp(int op, const InterpStep* steps, int nsteps, uint64_t run, uin
     case GLOO_HIP_PRODUCT: plan_interp_kernel<Tr, GLOO_HIP_PRODUCT><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt); break;
     case GLOO_HIP_MAX: plan_interp_kernel<Tr, GLOO_HIP_MAX><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt); break;
     case GLOO_HIP_MIN: plan_interp_kernel<Tr, GLOO_HIP_MIN><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt); break;
-    default: return GLOO_HIP_EINVAL_OP;
+    default:
+      return by_bitwise_op<Tr>(op, [&](auto o) {
+        plan_interp_kernel<Tr, decltype(o)::value><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt);
+        return GLOO_HIP_OK;
+      });
   }
   return GLOO_HIP_OK;
 }
@@ -1175,7 +1224,11 @@ int by_op_fold_send(int op, void* dst, const SrcList& list, int k, int mode, siz
     case GLOO_HIP_PRODUCT: return launch_fold_send<Tr, GLOO_HIP_PRODUCT>(dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_MAX: return launch_fold_send<Tr, GLOO_HIP_MAX>(dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_MIN: return launch_fold_send<Tr, GLOO_HIP_MIN>(dst, list, k, mode, n, F, epoch, s);
-    default: return set_error(GLOO_HIP_EINVAL_OP, "fold+forward needs a built-in op");
+    default: {
+      const int rc = by_bitwise_op<Tr>(
+          op, [&](auto o) { return launch_fold_send<Tr, decltype(o)::value>(dst, list, k, mode, n, F, epoch, s); });
+      return rc == GLOO_HIP_EINVAL_OP ? set_error(rc, "fold+forward needs a built-in op") : rc;
+    }
   }
 }
 
@@ -1275,7 +1328,10 @@ int by_op3(int op, void* c, const void* a, const void* b, size_t n, hipStream_t 
     case GLOO_HIP_PRODUCT: return launch3<Tr, GLOO_HIP_PRODUCT>(c, a, b, n, s);
     case GLOO_HIP_MAX: return launch3<Tr, GLOO_HIP_MAX>(c, a, b, n, s);
     case GLOO_HIP_MIN: return launch3<Tr, GLOO_HIP_MIN>(c, a, b, n, s);
-    default: return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+    default: {
+      const int rc = by_bitwise_op<Tr>(op, [&](auto o) { return launch3<Tr, decltype(o)::value>(c, a, b, n, s); });
+      return rc == GLOO_HIP_EINVAL_OP ? set_error(rc, "unknown reduction op") : rc;
+    }
   }
 }
 
@@ -1286,13 +1342,32 @@ int by_op_multi(int op, void* d, const void* const* srcs, int k, size_t n, hipSt
     case GLOO_HIP_PRODUCT: return launch_multi<Tr, GLOO_HIP_PRODUCT, MODE>(d, srcs, k, n, s);
     case GLOO_HIP_MAX: return launch_multi<Tr, GLOO_HIP_MAX, MODE>(d, srcs, k, n, s);
     case GLOO_HIP_MIN: return launch_multi<Tr, GLOO_HIP_MIN, MODE>(d, srcs, k, n, s);
-    default: return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+    default: {
+      const int rc =
+          by_bitwise_op<Tr>(op, [&](auto o) { return launch_multi<Tr, decltype(o)::value, MODE>(d, srcs, k, n, s); });
+      return rc == GLOO_HIP_EINVAL_OP ? set_error(rc, "unknown reduction op") : rc;
+    }
+  }
+}
+
+inline bool isBitwiseOp(int op) { return op >= GLOO_HIP_BAND && op <= GLOO_HIP_BXOR; }
+inline bool isIntegerDtype(int dtype) { return dtype >= GLOO_HIP_I8 && dtype <= GLOO_HIP_U64; }
+
+// The dtype whose kernels run `op`: a bitwise op on a signed integer dtype runs
+// the unsigned twin's (kHasBitwise); every other pair is left as it is.
+inline int bitwiseKernelDtype(int op, int dtype) {
+  if (!isBitwiseOp(op)) return dtype;
+  switch (dtype) {
+    case GLOO_HIP_I8: return GLOO_HIP_U8;
+    case GLOO_HIP_I32: return GLOO_HIP_U32;
+    case GLOO_HIP_I64: return GLOO_HIP_U64;
+    default: return dtype;
   }
 }
 
 int dispatch3(int op, int dtype, void* c, const void* a, const void* b, size_t n,
               hipStream_t s) {
-  switch (dtype) {
+  switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: return by_op3<TrI8>(op, c, a, b, n, s);
     case GLOO_HIP_U8: return by_op3<TrU8>(op, c, a, b, n, s);
     case GLOO_HIP_I32: return by_op3<TrI32>(op, c, a, b, n, s);
@@ -1310,7 +1385,7 @@ int dispatch3(int op, int dtype, void* c, const void* a, const void* b, size_t n
 template <int MODE = 0>
 int dispatch_multi(int op, int dtype, void* d, const void* const* srcs, int k, size_t n,
                    hipStream_t s) {
-  switch (dtype) {
+  switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: return by_op_multi<TrI8, MODE>(op, d, srcs, k, n, s);
     case GLOO_HIP_U8: return by_op_multi<TrU8, MODE>(op, d, srcs, k, n, s);
     case GLOO_HIP_I32: return by_op_multi<TrI32, MODE>(op, d, srcs, k, n, s);
@@ -1375,7 +1450,21 @@ std::vector<CustomEntry>& customOps() {
   return v;
 }
 
-bool isBuiltinOp(int op) { return op >= GLOO_HIP_SUM && op <= GLOO_HIP_MIN; }
+bool isBuiltinOp(int op, int dtype) {
+  if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return false;
+  if (op >= GLOO_HIP_SUM && op <= GLOO_HIP_MIN) return true;
+  return isBitwiseOp(op) && isIntegerDtype(dtype);
+}
+
+int checkBitwiseDtype(int op, int dtype) {
+  if (!isBitwiseOp(op) || dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES || isIntegerDtype(dtype)) return GLOO_HIP_OK;
+  static const char* const kOps[] = {"band", "bor", "bxor"};
+  static const char* const kDtypes[GLOO_HIP_NUM_DTYPES] = {"i8",  "u8",  "i32",  "u32", "i64",
+                                                          "u64", "f16", "bf16", "f32", "f64"};
+  return setError(GLOO_HIP_EINVAL_OP, std::string("reduction op ") + kOps[op - GLOO_HIP_BAND] +
+                                          " is not defined for dtype " + kDtypes[dtype] +
+                                          " (the bitwise ops take the integer dtypes)");
+}
 
 bool customOp(int op, gloo_hip_custom_fn* fn, void** user) {
   if (op < GLOO_HIP_CUSTOM) return false;
@@ -1462,7 +1551,7 @@ int launchFoldSend(int op, int dtype, void* dst, const void* const* srcs, int k,
     F.flag[r] = fwd[r].flag;
     F.seq[r] = fwd[r].seq;
   }
-  switch (dtype) {
+  switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: return by_op_fold_send<TrI8>(op, dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_U8: return by_op_fold_send<TrU8>(op, dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_I32: return by_op_fold_send<TrI32>(op, dst, list, k, mode, n, F, epoch, s);
@@ -1501,7 +1590,7 @@ int launchFusedSmall(int op, int dtype, void* dst, const void* src, size_t n, co
                      Seq waitTarget, uint64_t timeoutTicks, uint32_t* err, uint64_t* sigFlag, Seq sigValue,
                      const uint64_t* epoch, hipStream_t s) {
   int rc;
-  switch (dtype) {
+  switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: rc = launch_fused<TrI8>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     case GLOO_HIP_U8: rc = launch_fused<TrU8>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     case GLOO_HIP_I32: rc = launch_fused<TrI32>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
@@ -1525,7 +1614,7 @@ int launchPlanInterp(int op, int dtype, const InterpStep* steps, int nsteps, uin
   if (nsteps < 0 || nsteps > kInterpMaxSteps) return set_error(GLOO_HIP_EINVAL_ARG, "interpreter: bad step count");
   if (G < 1 || G > kMaxSlices) return set_error(GLOO_HIP_EINVAL_ARG, "interpreter: bad slice count");
   int rc;
-  switch (dtype) {
+  switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: rc = launch_interp<TrI8>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
     case GLOO_HIP_U8: rc = launch_interp<TrU8>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
     case GLOO_HIP_I32: rc = launch_interp<TrI32>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
@@ -1553,8 +1642,9 @@ int gloo_hip_reduce3(int op, int dtype, void* c, const void* a, const void* b, s
   gloo_hip_custom_fn cfn = nullptr;
   void* cuser = nullptr;
   const bool custom = customOp(op, &cfn, &cuser);
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
   if (n == 0) {
-    if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_MIN)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+    if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_BXOR)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
     if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
     return GLOO_HIP_OK;
   }
@@ -1608,7 +1698,8 @@ int gloo_hip_reduce_multi(int op, int dtype, void* dst, const void* const* srcs,
   gloo_hip_custom_fn cfn = nullptr;
   void* cuser = nullptr;
   const bool custom = customOp(op, &cfn, &cuser);
-  if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_MIN)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+  if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_BXOR)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
   if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   if (n == 0) return GLOO_HIP_OK;
   if (!dst || !srcs) return set_error(GLOO_HIP_EINVAL_PTR, "null buffer pointer");
@@ -1623,6 +1714,13 @@ size_t gloo_hip_dtype_size(int dtype) {
 }
 
 
+
+int gloo_hip_op_supported(int op, int dtype) {
+  gloo_hip_custom_fn cfn = nullptr;
+  void* cuser = nullptr;
+  if (isBuiltinOp(op, dtype)) return 1;
+  return dtype >= 0 && dtype < GLOO_HIP_NUM_DTYPES && customOp(op, &cfn, &cuser) ? 1 : 0;
+}
 
 int gloo_hip_set_variant(int variant) {
   const int prev = g_variant;

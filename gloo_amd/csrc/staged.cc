@@ -77,7 +77,8 @@ extern "C" int gloo_hip_reduce_staged(int op, int dtype, void* host_dst, const v
     if (es == 0) return setError(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
     gloo_hip_custom_fn cfn;
     void* cuser;
-    if (!isBuiltinOp(op) && !customOp(op, &cfn, &cuser)) return setError(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+    if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+    if (!isBuiltinOp(op, dtype) && !customOp(op, &cfn, &cuser)) return setError(GLOO_HIP_EINVAL_OP, "unknown reduction op");
     if (n == 0) return GLOO_HIP_OK;
     if (!host_dst || !host_src || !dev_dst || !dev_src) return setError(GLOO_HIP_EINVAL_PTR, "null buffer pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);

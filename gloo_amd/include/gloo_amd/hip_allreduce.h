@@ -54,8 +54,17 @@ template <> struct DType<bfloat16> { static constexpr int value = GLOO_HIP_BF16;
 template <> struct DType<float> { static constexpr int value = GLOO_HIP_F32; };
 template <> struct DType<double> { static constexpr int value = GLOO_HIP_F64; };
 
-// gloo::ReductionType values (gloo/algorithm.h:49-57).
-enum ReductionType { SUM = GLOO_HIP_SUM, PRODUCT = GLOO_HIP_PRODUCT, MAX = GLOO_HIP_MAX, MIN = GLOO_HIP_MIN };
+// gloo::ReductionType values (gloo/algorithm.h:49-57), extended by the
+// bitwise ops of the integer types (include/gloo_amd.h gloo_hip_op_t).
+enum ReductionType {
+  SUM = GLOO_HIP_SUM,
+  PRODUCT = GLOO_HIP_PRODUCT,
+  MAX = GLOO_HIP_MAX,
+  MIN = GLOO_HIP_MIN,
+  BAND = GLOO_HIP_BAND,
+  BOR = GLOO_HIP_BOR,
+  BXOR = GLOO_HIP_BXOR,
+};
 
 // Device reduction function: call() enqueues dst = dst op src on `stream`
 // (the device overload of CudaReductionFunction<T>::call, gloo/cuda.h:326-333).
@@ -66,6 +75,11 @@ class HipReductionFunction {
   static const HipReductionFunction<T>* product;
   static const HipReductionFunction<T>* min;
   static const HipReductionFunction<T>* max;
+  // integer T only: call() and the algorithms' constructors refuse them for
+  // float16, bfloat16, float and double (GLOO_HIP_EINVAL_OP)
+  static const HipReductionFunction<T>* band;
+  static const HipReductionFunction<T>* bor;
+  static const HipReductionFunction<T>* bxor;
 
   explicit HipReductionFunction(ReductionType t) : type_(t) {}
   ReductionType type() const { return type_; }
@@ -85,6 +99,12 @@ template <typename T>
 const HipReductionFunction<T>* HipReductionFunction<T>::min = new HipReductionFunction<T>(MIN);
 template <typename T>
 const HipReductionFunction<T>* HipReductionFunction<T>::max = new HipReductionFunction<T>(MAX);
+template <typename T>
+const HipReductionFunction<T>* HipReductionFunction<T>::band = new HipReductionFunction<T>(BAND);
+template <typename T>
+const HipReductionFunction<T>* HipReductionFunction<T>::bor = new HipReductionFunction<T>(BOR);
+template <typename T>
+const HipReductionFunction<T>* HipReductionFunction<T>::bxor = new HipReductionFunction<T>(BXOR);
 
 // gloo::Algorithm (gloo/algorithm.h:20-38).
 class Algorithm {

@@ -189,8 +189,13 @@ int launchStampInit(uint64_t* stamps, int k, hipStream_t stream);
 
 // Registered custom reductions (gloo_hip_register_op): op codes
 // GLOO_HIP_CUSTOM + i.  customOp fills fn/user and returns true for a
-// registered code.
-bool isBuiltinOp(int op);
+// registered code.  isBuiltinOp: the kernels implement `op` on `dtype` (the
+// arithmetic ops on every dtype, the bitwise ops on the integer dtypes).
+// checkBitwiseDtype: GLOO_HIP_EINVAL_OP, with a message naming both, for a
+// bitwise op on a floating dtype; GLOO_HIP_OK for every other pair, valid or
+// not (the caller's own op and dtype checks follow).  No GPU call in either.
+bool isBuiltinOp(int op, int dtype);
+int checkBitwiseDtype(int op, int dtype);
 bool customOp(int op, gloo_hip_custom_fn* fn, void** user);
 
 int launchFold(int op, int dtype, void* dst, const void* const* srcs, int k, size_t n, int mode,

@@ -48,12 +48,27 @@
 extern "C" {
 #endif
 
-/* Mirrors gloo::ReductionType (gloo/algorithm.h:49-57). */
+/* SUM..MIN mirror gloo::ReductionType (gloo/algorithm.h:49-57).  BAND, BOR
+ * and BXOR extend it; they do not mirror it (the reference's enum stops at
+ * MIN).  Their model is the BAND / BOR / BXOR of PyTorch's ReduceOp, which
+ * its Gloo process group builds from custom functions:
+ *   BAND  c = a & b      BOR  c = a | b      BXOR  c = a ^ b
+ * on the element's bits, exact in every schedule and fold order.  They are
+ * defined for I8, U8, I32, U32, I64, U64; with F16, BF16, F32 or F64 every
+ * entry point that takes an op returns GLOO_HIP_EINVAL_OP (the message names
+ * the op and the dtype) before it looks at n or at a pointer, and the
+ * collective entry points (gloo_hip_algorithm_create*, gloo_hip_allreduce,
+ * gloo_hip_reduce_to_root) before any exchange with a peer, so every rank
+ * fails locally.  They take every kernel path the arithmetic ops take.
+ * Codes 8..999 are invalid. */
 typedef enum {
   GLOO_HIP_SUM = 1,
   GLOO_HIP_PRODUCT = 2,
   GLOO_HIP_MAX = 3,
   GLOO_HIP_MIN = 4,
+  GLOO_HIP_BAND = 5,
+  GLOO_HIP_BOR = 6,
+  GLOO_HIP_BXOR = 7,
 } gloo_hip_op_t;
 
 typedef enum {
@@ -148,6 +163,12 @@ int gloo_hip_copy_kernel(void* dst, const void* src, size_t bytes, unsigned bloc
  * at most `blocks` workgroups (0: 64, the executor's per-peer default). */
 int gloo_hip_copy_kernel_multi(void* const* dsts, const void* const* srcs, const size_t* bytes, int n,
                                unsigned blocks, gloo_hip_stream_t stream);
+
+/* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
+ * is defined for (SUM..MIN on all ten, BAND / BOR / BXOR on the six integer
+ * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
+ * touches the GPU. */
+int gloo_hip_op_supported(int op, int dtype);
 
 /* Size in bytes of one element of `dtype`, or 0 when dtype is unknown. */
 size_t gloo_hip_dtype_size(int dtype);
