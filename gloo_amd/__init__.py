@@ -44,11 +44,13 @@ class DType(enum.IntEnum):
     BF16 = 7
     F32 = 8
     F64 = 9
+    F8E4M3 = 10  # OCP e4m3fn (torch.float8_e4m3fn)
+    F8E5M2 = 11  # OCP e5m2 (torch.float8_e5m2)
 
 
 DTYPE_NAMES = {"i8": DType.I8, "u8": DType.U8, "i32": DType.I32, "u32": DType.U32,
                "i64": DType.I64, "u64": DType.U64, "f16": DType.F16, "bf16": DType.BF16,
-               "f32": DType.F32, "f64": DType.F64}
+               "f32": DType.F32, "f64": DType.F64, "f8e4m3": DType.F8E4M3, "f8e5m2": DType.F8E5M2}
 OP_NAMES = {"sum": ReductionType.SUM, "product": ReductionType.PRODUCT,
             "max": ReductionType.MAX, "min": ReductionType.MIN,
             "band": ReductionType.BAND, "bor": ReductionType.BOR, "bxor": ReductionType.BXOR}
@@ -191,6 +193,10 @@ def _torch_dtype_code(t):
         m[torch.uint32] = DType.U32
     if hasattr(torch, "uint64"):
         m[torch.uint64] = DType.U64
+    if hasattr(torch, "float8_e4m3fn"):
+        m[torch.float8_e4m3fn] = DType.F8E4M3
+    if hasattr(torch, "float8_e5m2"):
+        m[torch.float8_e5m2] = DType.F8E5M2
     if t.dtype not in m:
         raise TypeError(f"unsupported dtype {t.dtype}")
     return m[t.dtype]

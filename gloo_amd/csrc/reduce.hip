@@ -163,6 +163,66 @@ struct TrBF16 {
   }
 };
 
+// OCP FP8 held as raw bytes: e4m3fn (E5M2 = false; no infinity, NaN 0x7F /
+// 0xFF, largest finite 448) and e5m2 (infinity 0x7C, NaNs 0x7D..0x7F).  The
+// model is c10::Float8_e4m3fn / c10::Float8_e5m2: widen to f32 (exact), one
+// f32 op, round to nearest even back, overflow not saturated.  gfx950 has the
+// converts natively (v_cvt_f32_fp8 / _bf8, v_cvt_pk_fp8_f32 / _bf8_f32); this
+// is the one arithmetic path of the file that no older gfx9 would run.
+//
+// What the narrowing convert does above the largest finite value and which
+// NaN byte it emits depends on a mode-register bit (saturate or not) this
+// code neither reads nor sets, so the contract's rule is laid over the
+// convert with compares on the f32 result's bits, valid whatever the bit
+// says: below the overflow threshold round-to-nearest-even gives at most the
+// largest finite value in either mode, so the convert's byte stands; from the
+// threshold up the byte is the rule's (e4m3fn |r| > 464: NaN with r's sign;
+// e5m2 |r| >= 61440, infinities included: infinity with r's sign); an f32 NaN
+// is 0x7F in both formats (include/gloo_amd.h: torch's own byte there carries
+// whichever operand's sign one x86 build picked).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <bool E5M2>
+struct F8Traits {
+  using Storage = uint8_t;
+  static constexpr bool kIntegral = false;
+  static constexpr uint32_t kOverBits = E5M2 ? 0x47700000u /* 61440.0f */ : 0x43E80001u /* just above 464.0f */;
+  static constexpr uint32_t kOverByte = E5M2 ? 0x7Cu : 0x7Fu;
+  __device__ static __forceinline__ float widen(uint8_t x) {
+    if constexpr (E5M2) return __builtin_amdgcn_cvt_f32_bf8((int)x, 0);
+    else return __builtin_amdgcn_cvt_f32_fp8((int)x, 0);
+  }
+  // elements 2*HI, 2*HI + 1 of a dword of four
+  template <bool HI>
+  __device__ static __forceinline__ f32x2 widen2(uint32_t w) {
+    if constexpr (E5M2) return __builtin_amdgcn_cvt_pk_f32_bf8((int)w, HI);
+    else return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI);
+  }
+  // x, y converted into half HI of `old`, the other half kept
+  template <bool HI>
+  __device__ static __forceinline__ uint32_t narrow2(float x, float y, uint32_t old) {
+    if constexpr (E5M2) return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(x, y, (int)old, HI);
+    else return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x, y, (int)old, HI);
+  }
+  // the convert's byte does not stand: r is a NaN or at / above the threshold
+  __device__ static __forceinline__ bool special(float r) {
+    if constexpr (E5M2) return !(__builtin_fabsf(r) < 61440.0f);
+    else return !(__builtin_fabsf(r) <= 464.0f);
+  }
+  __device__ static __forceinline__ uint8_t narrow(float r) {
+    const uint32_t bits = __builtin_bit_cast(uint32_t, r), mag = bits & 0x7FFFFFFFu;
+    uint32_t h = narrow2<false>(r, r, 0) & 0xFFu;
+    h = mag >= kOverBits ? (((bits >> 24) & 0x80u) | kOverByte) : h;
+    h = mag > 0x7F800000u ? 0x7Fu : h;
+    return (uint8_t)h;
+  }
+  __device__ static __forceinline__ uint8_t sum(uint8_t a, uint8_t b) { return narrow(widen(a) + widen(b)); }
+  __device__ static __forceinline__ uint8_t product(uint8_t a, uint8_t b) { return narrow(widen(a) * widen(b)); }
+  __device__ static __forceinline__ uint8_t max(uint8_t a, uint8_t b) { return (widen(a) < widen(b)) ? b : a; }
+  __device__ static __forceinline__ uint8_t min(uint8_t a, uint8_t b) { return (widen(b) < widen(a)) ? b : a; }
+};
+using TrF8E4M3 = F8Traits<false>;
+using TrF8E5M2 = F8Traits<true>;
+
 template <class Tr, int OP>
 __device__ __forceinline__ typename Tr::Storage apply(typename Tr::Storage a,
                                                       typename Tr::Storage b) {
@@ -286,6 +346,48 @@ __device__ __forceinline__ u32x4 apply_packet<TrF16, GLOO_HIP_SUM>(u32x4 a, u32x
 template <>
 __device__ __forceinline__ u32x4 apply_packet<TrF16, GLOO_HIP_PRODUCT>(u32x4 a, u32x4 b) {
   return f16_pk_packet<GLOO_HIP_PRODUCT>(a, b);
+}
+
+// FP8 SUM / PRODUCT, per dword of four elements: two word-selected packed
+// widens per operand (v_cvt_pk_f32_fp8 / _bf8), two v_pk_add_f32 /
+// v_pk_mul_f32, two packed narrows into the low and the high half: 12 VALU
+// instructions plus four compares (F8Traits::special, OR-ed on the scalar
+// unit) that find a result the convert's byte does not stand for.  Such a
+// packet (overflow, infinity or NaN: rare in real buckets) is redone element
+// by element with F8Traits' full rule; the packed f32 ops are the scalar
+// ones, so both forms give the same bytes everywhere else.
+template <class Tr, int OP>
+__device__ __forceinline__ uint32_t f8_pk_dword(uint32_t a, uint32_t b, bool& special) {
+  const f32x2 alo = Tr::template widen2<false>(a), ahi = Tr::template widen2<true>(a);
+  const f32x2 blo = Tr::template widen2<false>(b), bhi = Tr::template widen2<true>(b);
+  const f32x2 lo = OP == GLOO_HIP_SUM ? alo + blo : alo * blo;
+  const f32x2 hi = OP == GLOO_HIP_SUM ? ahi + bhi : ahi * bhi;
+  special = special || Tr::special(lo.x) || Tr::special(lo.y) || Tr::special(hi.x) || Tr::special(hi.y);
+  return Tr::template narrow2<true>(hi.x, hi.y, Tr::template narrow2<false>(lo.x, lo.y, 0));
+}
+template <class Tr, int OP>
+__device__ __forceinline__ u32x4 f8_pk_packet(u32x4 a, u32x4 b) {
+  bool special = false;
+  u32x4 r = u32x4{f8_pk_dword<Tr, OP>(a.x, b.x, special), f8_pk_dword<Tr, OP>(a.y, b.y, special),
+                  f8_pk_dword<Tr, OP>(a.z, b.z, special), f8_pk_dword<Tr, OP>(a.w, b.w, special)};
+  if (__builtin_expect(special, 0)) r = generic_packet<Tr, OP>(a, b);
+  return r;
+}
+template <>
+__device__ __forceinline__ u32x4 apply_packet<TrF8E4M3, GLOO_HIP_SUM>(u32x4 a, u32x4 b) {
+  return f8_pk_packet<TrF8E4M3, GLOO_HIP_SUM>(a, b);
+}
+template <>
+__device__ __forceinline__ u32x4 apply_packet<TrF8E4M3, GLOO_HIP_PRODUCT>(u32x4 a, u32x4 b) {
+  return f8_pk_packet<TrF8E4M3, GLOO_HIP_PRODUCT>(a, b);
+}
+template <>
+__device__ __forceinline__ u32x4 apply_packet<TrF8E5M2, GLOO_HIP_SUM>(u32x4 a, u32x4 b) {
+  return f8_pk_packet<TrF8E5M2, GLOO_HIP_SUM>(a, b);
+}
+template <>
+__device__ __forceinline__ u32x4 apply_packet<TrF8E5M2, GLOO_HIP_PRODUCT>(u32x4 a, u32x4 b) {
+  return f8_pk_packet<TrF8E5M2, GLOO_HIP_PRODUCT>(a, b);
 }
 
 // Buffer resources.  Each workgroup builds descriptors whose base is its own
@@ -1378,6 +1480,8 @@ int dispatch3(int op, int dtype, void* c, const void* a, const void* b, size_t n
     case GLOO_HIP_BF16: return by_op3<TrBF16>(op, c, a, b, n, s);
     case GLOO_HIP_F32: return by_op3<TrF32>(op, c, a, b, n, s);
     case GLOO_HIP_F64: return by_op3<TrF64>(op, c, a, b, n, s);
+    case GLOO_HIP_F8E4M3: return by_op3<TrF8E4M3>(op, c, a, b, n, s);
+    case GLOO_HIP_F8E5M2: return by_op3<TrF8E5M2>(op, c, a, b, n, s);
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
 }
@@ -1396,6 +1500,8 @@ int dispatch_multi(int op, int dtype, void* d, const void* const* srcs, int k, s
     case GLOO_HIP_BF16: return by_op_multi<TrBF16, MODE>(op, d, srcs, k, n, s);
     case GLOO_HIP_F32: return by_op_multi<TrF32, MODE>(op, d, srcs, k, n, s);
     case GLOO_HIP_F64: return by_op_multi<TrF64, MODE>(op, d, srcs, k, n, s);
+    case GLOO_HIP_F8E4M3: return by_op_multi<TrF8E4M3, MODE>(op, d, srcs, k, n, s);
+    case GLOO_HIP_F8E5M2: return by_op_multi<TrF8E5M2, MODE>(op, d, srcs, k, n, s);
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
 }
@@ -1460,7 +1566,8 @@ int checkBitwiseDtype(int op, int dtype) {
   if (!isBitwiseOp(op) || dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES || isIntegerDtype(dtype)) return GLOO_HIP_OK;
   static const char* const kOps[] = {"band", "bor", "bxor"};
   static const char* const kDtypes[GLOO_HIP_NUM_DTYPES] = {"i8",  "u8",  "i32",  "u32", "i64",
-                                                          "u64", "f16", "bf16", "f32", "f64"};
+                                                          "u64", "f16", "bf16", "f32", "f64",
+                                                          "f8e4m3", "f8e5m2"};
   return setError(GLOO_HIP_EINVAL_OP, std::string("reduction op ") + kOps[op - GLOO_HIP_BAND] +
                                           " is not defined for dtype " + kDtypes[dtype] +
                                           " (the bitwise ops take the integer dtypes)");
@@ -1562,6 +1669,8 @@ int launchFoldSend(int op, int dtype, void* dst, const void* const* srcs, int k,
     case GLOO_HIP_BF16: return by_op_fold_send<TrBF16>(op, dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_F32: return by_op_fold_send<TrF32>(op, dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_F64: return by_op_fold_send<TrF64>(op, dst, list, k, mode, n, F, epoch, s);
+    case GLOO_HIP_F8E4M3: return by_op_fold_send<TrF8E4M3>(op, dst, list, k, mode, n, F, epoch, s);
+    case GLOO_HIP_F8E5M2: return by_op_fold_send<TrF8E5M2>(op, dst, list, k, mode, n, F, epoch, s);
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
 }
@@ -1601,6 +1710,8 @@ int launchFusedSmall(int op, int dtype, void* dst, const void* src, size_t n, co
     case GLOO_HIP_BF16: rc = launch_fused<TrBF16>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     case GLOO_HIP_F32: rc = launch_fused<TrF32>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     case GLOO_HIP_F64: rc = launch_fused<TrF64>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
+    case GLOO_HIP_F8E4M3: rc = launch_fused<TrF8E4M3>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
+    case GLOO_HIP_F8E5M2: rc = launch_fused<TrF8E5M2>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
   if (rc != GLOO_HIP_OK) return set_error(rc, "fused step: bad op");
@@ -1625,6 +1736,8 @@ int launchPlanInterp(int op, int dtype, const InterpStep* steps, int nsteps, uin
     case GLOO_HIP_BF16: rc = launch_interp<TrBF16>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
     case GLOO_HIP_F32: rc = launch_interp<TrF32>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
     case GLOO_HIP_F64: rc = launch_interp<TrF64>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
+    case GLOO_HIP_F8E4M3: rc = launch_interp<TrF8E4M3>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
+    case GLOO_HIP_F8E5M2: rc = launch_interp<TrF8E5M2>(op, steps, nsteps, run, tt, err, G, s, done, doneTicket); break;
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
   if (rc != GLOO_HIP_OK) return set_error(rc, "interpreter: bad op");
@@ -1708,7 +1821,7 @@ int gloo_hip_reduce_multi(int op, int dtype, void* dst, const void* const* srcs,
 }
 
 size_t gloo_hip_dtype_size(int dtype) {
-  static const size_t kSizes[GLOO_HIP_NUM_DTYPES] = {1, 1, 4, 4, 8, 8, 2, 2, 4, 8};
+  static const size_t kSizes[GLOO_HIP_NUM_DTYPES] = {1, 1, 4, 4, 8, 8, 2, 2, 4, 8, 1, 1};
   if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return 0;
   return kSizes[dtype];
 }

@@ -39,7 +39,9 @@
 // is ordered after the collective, so the caller synchronises with them.
 //
 // Element types: the reference's CUDA instantiations (gloo/cuda.cu:265-272),
-// plus c10::BFloat16 when built with GLOO_USE_TORCH_DTYPES (cuda.cu:394-401).
+// plus c10::BFloat16 when built with GLOO_USE_TORCH_DTYPES (cuda.cu:394-401)
+// and, under the same switch, c10::Float8_e4m3fn / c10::Float8_e5m2 (this
+// library's own extension: include/gloo_amd.h).
 // Reductions: the built-in ReductionType values run the library's kernels; a
 // CUSTOM reduction is a gloo::HipReductionFunction<T> carrying a device
 // function (the device half of CudaReductionFunction, gloo/cuda.h:286-358).
@@ -65,6 +67,8 @@
 
 #if GLOO_USE_TORCH_DTYPES
 #include <c10/util/BFloat16.h>
+#include <c10/util/Float8_e4m3fn.h>
+#include <c10/util/Float8_e5m2.h>
 #endif
 
 #include <map>
@@ -97,6 +101,8 @@ template <> struct DType<float> { static constexpr int value = GLOO_HIP_F32; };
 template <> struct DType<double> { static constexpr int value = GLOO_HIP_F64; };
 #if GLOO_USE_TORCH_DTYPES
 template <> struct DType<c10::BFloat16> { static constexpr int value = GLOO_HIP_BF16; };
+template <> struct DType<c10::Float8_e4m3fn> { static constexpr int value = GLOO_HIP_F8E4M3; };
+template <> struct DType<c10::Float8_e5m2> { static constexpr int value = GLOO_HIP_F8E5M2; };
 #endif
 
 // CUSTOM reductions: ReductionFunction<T> has no virtual members, so a

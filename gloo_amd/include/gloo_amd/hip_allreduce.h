@@ -41,6 +41,13 @@ struct float16 {
 struct bfloat16 {
   uint16_t x;
 };
+// OCP FP8 storage types (c10::Float8_e4m3fn, c10::Float8_e5m2).
+struct float8_e4m3fn {
+  uint8_t x;
+};
+struct float8_e5m2 {
+  uint8_t x;
+};
 
 template <typename T> struct DType;
 template <> struct DType<int8_t> { static constexpr int value = GLOO_HIP_I8; };
@@ -53,6 +60,8 @@ template <> struct DType<float16> { static constexpr int value = GLOO_HIP_F16; }
 template <> struct DType<bfloat16> { static constexpr int value = GLOO_HIP_BF16; };
 template <> struct DType<float> { static constexpr int value = GLOO_HIP_F32; };
 template <> struct DType<double> { static constexpr int value = GLOO_HIP_F64; };
+template <> struct DType<float8_e4m3fn> { static constexpr int value = GLOO_HIP_F8E4M3; };
+template <> struct DType<float8_e5m2> { static constexpr int value = GLOO_HIP_F8E5M2; };
 
 // gloo::ReductionType values (gloo/algorithm.h:49-57), extended by the
 // bitwise ops of the integer types (include/gloo_amd.h gloo_hip_op_t).
@@ -76,7 +85,8 @@ class HipReductionFunction {
   static const HipReductionFunction<T>* min;
   static const HipReductionFunction<T>* max;
   // integer T only: call() and the algorithms' constructors refuse them for
-  // float16, bfloat16, float and double (GLOO_HIP_EINVAL_OP)
+  // float16, bfloat16, float, double and the two float8 types
+  // (GLOO_HIP_EINVAL_OP)
   static const HipReductionFunction<T>* band;
   static const HipReductionFunction<T>* bor;
   static const HipReductionFunction<T>* bxor;

@@ -54,7 +54,8 @@ extern "C" {
  * its Gloo process group builds from custom functions:
  *   BAND  c = a & b      BOR  c = a | b      BXOR  c = a ^ b
  * on the element's bits, exact in every schedule and fold order.  They are
- * defined for I8, U8, I32, U32, I64, U64; with F16, BF16, F32 or F64 every
+ * defined for I8, U8, I32, U32, I64, U64; with F16, BF16, F32, F64, F8E4M3
+ * or F8E5M2 every
  * entry point that takes an op returns GLOO_HIP_EINVAL_OP (the message names
  * the op and the dtype) before it looks at n or at a pointer, and the
  * collective entry points (gloo_hip_algorithm_create*, gloo_hip_allreduce,
@@ -82,8 +83,37 @@ typedef enum {
   GLOO_HIP_BF16 = 7,
   GLOO_HIP_F32 = 8,
   GLOO_HIP_F64 = 9,
-  GLOO_HIP_NUM_DTYPES = 10,
+  GLOO_HIP_F8E4M3 = 10, /* OCP e4m3fn, torch.float8_e4m3fn */
+  GLOO_HIP_F8E5M2 = 11, /* OCP e5m2, torch.float8_e5m2 */
+  GLOO_HIP_NUM_DTYPES = 12,
 } gloo_hip_dtype_t;
+
+/* F8E4M3 and F8E5M2 (1 byte each; the FNUZ variants are not part of this)
+ * extend the reference's type list; they do not mirror it.  Their model is
+ * c10::Float8_e4m3fn / c10::Float8_e5m2, i.e. torch on the CPU, as
+ * c10::BFloat16 is for BF16.
+ *   e4m3fn: no infinity, NaN is 0x7F / 0xFF, the largest finite value is 448.
+ *   e5m2:   infinity is 0x7C / 0xFC, NaNs are 0x7D..0x7F / 0xFD..0xFF.
+ *   SUM, PRODUCT: both operands widened to f32 (exact), one IEEE f32 op,
+ *     rounded to nearest even back to the format with c10's overflow rule,
+ *     which does not saturate: e4m3fn, a finite r with |r| > 464 becomes the
+ *     NaN with r's sign (0x7F / 0xFF; 464 itself rounds to 448 = 0x7E); e5m2,
+ *     |r| >= 61440 becomes the infinity with r's sign.
+ *     Where the f32 result r is itself a NaN (a NaN operand, inf - inf,
+ *     0 * inf) the stored byte is 0x7F in both formats.  torch's own byte
+ *     there carries the sign of whichever operand its x86 vector code picked
+ *     (the second for +, the first for *, negative for an invalid operation):
+ *     an artefact of one build, not a rule; the same reasoning as BF16's
+ *     canonical 0x7FC0.
+ *   MAX, MIN: (a < b) ? b : a and (b < a) ? b : a compared in f32, the raw
+ *     operand byte copied, as for F16 / BF16: a NaN in a stays, a NaN in b
+ *     is ignored, max(+0, -0) is +0.
+ *   Multi-source folds round to the format after every op (left to right, or
+ *     as a tree where the schedule folds as one), so a k-source fold is
+ *     byte-identical to k - 1 two-operand calls and every schedule agrees
+ *     with its mesh form.
+ *   BAND / BOR / BXOR are refused (GLOO_HIP_EINVAL_OP) as for the other
+ *     floating dtypes; registered custom ops take them like any known dtype. */
 
 /* Status codes: 0 = success, > 0 = a hipError_t, < 0 = argument error. */
 #define GLOO_HIP_OK 0
@@ -165,7 +195,7 @@ int gloo_hip_copy_kernel_multi(void* const* dsts, const void* const* srcs, const
                                unsigned blocks, gloo_hip_stream_t stream);
 
 /* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
- * is defined for (SUM..MIN on all ten, BAND / BOR / BXOR on the six integer
+ * is defined for (SUM..MIN on all twelve, BAND / BOR / BXOR on the six integer
  * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
  * touches the GPU. */
 int gloo_hip_op_supported(int op, int dtype);
