@@ -58,7 +58,8 @@ OP_NAMES = {"sum": ReductionType.SUM, "product": ReductionType.PRODUCT,
 EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
-            "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported")
+            "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
+            "gloo_hip_fanout_kernel")
 
 
 class GlooHipError(RuntimeError):
@@ -92,6 +93,7 @@ def _load():
     L.gloo_hip_copy_kernel.argtypes = [vp, vp, sz, ctypes.c_uint, vp]
     L.gloo_hip_copy_kernel_multi.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int,
                                              ctypes.c_uint, vp]
+    L.gloo_hip_fanout_kernel.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, sz, ctypes.c_uint, vp]
     return L
 
 
@@ -175,6 +177,13 @@ def copy_kernel_multi(dsts, srcs, nbytes, blocks=0, stream=0):
     vp = ctypes.c_void_p
     _check(lib.gloo_hip_copy_kernel_multi((vp * n)(*dsts), (vp * n)(*srcs), (ctypes.c_size_t * n)(*sizes), n,
                                           blocks, stream or None))
+
+
+def fanout_kernel(dsts, src, nbytes, blocks=0, stream=0):
+    """gloo_hip_fanout_kernel: one source to up to 8 destinations in one pass
+    (the broadcast root's fan-out without its flags)."""
+    n = len(dsts)
+    _check(lib.gloo_hip_fanout_kernel((ctypes.c_void_p * n)(*dsts), n, src, nbytes, blocks, stream or None))
 
 
 def set_variant(v):
@@ -261,7 +270,10 @@ ALGORITHMS = {"ring_chunked": 0, "halving_doubling": 1, "ring": 2, "local": 3,
               "reduce_scatter": 4, "bcube": 10,  # bcube: AllreduceBcube, recv_elems = [base]
               # CudaAllreduceHalvingDoubling with pipelineBroadcastAndReduce = true
               # (GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED): always on the reference's route
-              "halving_doubling_pipelined": 11}
+              "halving_doubling_pipelined": 11,
+              # CudaBroadcastOneToAll (GLOO_HIP_ALGO_BROADCAST): recv_elems = [root, root pointer];
+              # `op` is not used
+              "broadcast": 12}
 
 
 def _bind_collectives(L):
@@ -404,8 +416,8 @@ class Context:
         self._h = h
 
     def last_mode(self):
-        """How the latest function-style call (allreduce / reduce_to_root)
-        on this context ran (see Algorithm.mode)."""
+        """How the latest function-style call (allreduce / reduce_to_root /
+        broadcast) on this context ran (see Algorithm.mode)."""
         out = (ctypes.c_int * 4)()
         _check(lib.gloo_hip_context_mode(self._h, out))
         return _mode_dict(out)
@@ -429,23 +441,30 @@ class Algorithm:
     inboxes, the CudaHostWorkspace placement; gloo/cuda_workspace.h:20-31)."""
 
     def __init__(self, ctx, algo, op, dtype, ptrs, count, recv_elems=None, stream=0, workspace="device",
-                 streams=None, base=None):
+                 streams=None, base=None, root=None, root_pointer=None):
         """stream: one stream for the plan (0: the algorithm's own stream,
         and run() returns with outputs complete).  streams: one stream handle per
         pointer instead (the reference's `streams` argument,
         gloo/cuda_allreduce_ring_chunked.cc:55-67): run() orders pointer i
         after the work queued on streams[i], and every streams[i] after the
         collective.  base: AllreduceBcube's group size (gloo::Context::base,
-        gloo/context.h:28-33), the same as recv_elems=[base]."""
+        gloo/context.h:28-33), the same as recv_elems=[base].  root,
+        root_pointer: the broadcast's root rank and root pointer rank
+        (CudaBroadcastOneToAll's rootRank / rootPointerRank, 0 when absent),
+        the same as recv_elems=[root, root_pointer]."""
         self.ctx = ctx
         if base is not None:
             recv_elems = [int(base)]
+        a = ALGORITHMS[algo] if isinstance(algo, str) else int(algo)
+        if root is not None or root_pointer is not None:
+            recv_elems = [int(root or 0), int(root_pointer or 0)]
+        if (a & ~0x100) == ALGORITHMS["broadcast"]:  # the C side reads two entries
+            recv_elems = (list(recv_elems or []) + [0, 0])[:2]
         arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
         rp = None
         if recv_elems is not None:
             rp = (ctypes.c_int * len(recv_elems))(*[int(x) for x in recv_elems])
         h = ctypes.c_void_p()
-        a = ALGORITHMS[algo] if isinstance(algo, str) else int(algo)
         ws = WORKSPACES[workspace] if isinstance(workspace, str) else int(workspace)
         if streams is not None:
             sarr = (ctypes.c_void_p * max(1, len(streams)))(*[int(x) for x in streams])
@@ -572,3 +591,32 @@ def reduce_to_root(ctx, output, elements, dtype, root, op="sum", input=None, max
     o.tag = tag
     o.stream = stream or None
     _check(lib.gloo_hip_reduce_to_root(ctx._h, ctypes.byref(o)))
+
+
+# ---- new-style function API: gloo::broadcast(opts) -------------------------
+
+class BroadcastOptions(ctypes.Structure):
+    """gloo_hip_broadcast_options_t (mirrors gloo::BroadcastOptions, gloo/broadcast.h:16-87)."""
+    _fields_ = [("dtype", ctypes.c_int), ("input", ctypes.c_void_p), ("output", ctypes.c_void_p),
+                ("elements", ctypes.c_size_t), ("root", ctypes.c_int), ("tag", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p)]
+
+
+lib.gloo_hip_broadcast.argtypes = [ctypes.c_void_p, ctypes.POINTER(BroadcastOptions)]
+EXPORTED = EXPORTED + ("gloo_hip_broadcast",)
+
+
+def broadcast(ctx, output, elements, dtype, root, input=None, tag=0, stream=0):
+    """gloo::broadcast(opts) on device pointers, one-to-all from the root
+    (GLOO_HIP_ALGO_BROADCAST): every rank's output receives the bytes of the
+    root's input (of its output, when it gives no input).  input is used on
+    the root only."""
+    o = BroadcastOptions()
+    o.dtype = _as_dtype(dtype)
+    o.input = input or None
+    o.output = output
+    o.elements = int(elements)
+    o.root = int(root)
+    o.tag = tag
+    o.stream = stream or None
+    _check(lib.gloo_hip_broadcast(ctx._h, ctypes.byref(o)))

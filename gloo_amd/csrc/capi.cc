@@ -83,6 +83,31 @@ void runCached(gloo_hip_context_t ctx, int algo, int op, int dtype, const std::v
   ctx->last = it->second.get();
   it->second->run();
 }
+
+bool isBroadcast(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_BROADCAST; }
+
+// GLOO_HIP_ALGO_BROADCAST at the algorithm entry points.  Refused here,
+// before any exchange with a peer (every rank makes the same call and fails
+// alike): | GLOO_HIP_ALGO_MESH, a root outside [0, size), a root pointer
+// outside [0, nptrs).  The executor then gets {root} and the pointer list
+// with the root pointer first (order[i] = the caller's index of executor
+// pointer i), so LOCAL_BCAST's ptrs[i] = ptrs[0] is the reference's local
+// broadcast from devicePtrs_[rootPointerRank].  `op` is not used by a
+// broadcast; the executor's copy kernels get SUM, which every dtype has.
+void broadcastArgs(int algo, int size, const int* recv_elems, int nptrs, std::vector<int>* re,
+                   std::vector<int>* order, int* op) {
+  GLOO_AMD_ENFORCE(!(algo & GLOO_HIP_ALGO_MESH), "broadcast has no mesh form: algorithm ", algo,
+                   " (GLOO_HIP_ALGO_BROADCAST | GLOO_HIP_ALGO_MESH) is refused");
+  const int root = recv_elems ? recv_elems[0] : 0, rootPointer = recv_elems ? recv_elems[1] : 0;
+  GLOO_AMD_ENFORCE(root >= 0 && root < size, "broadcast: root rank ", root, " outside [0, ", size, ")");
+  GLOO_AMD_ENFORCE(rootPointer >= 0 && rootPointer < nptrs, "broadcast: root pointer ", rootPointer,
+                   " outside [0, ", nptrs, ")");
+  re->assign(1, root);
+  order->assign(1, rootPointer);
+  for (int i = 0; i < nptrs; i++)
+    if (i != rootPointer) order->push_back(i);
+  *op = GLOO_HIP_SUM;
+}
 }  // namespace
 
 extern "C" {
@@ -123,7 +148,8 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
                                  gloo_hip_algorithm_t* out) {
   // refused on this rank before any exchange: every rank makes the same call
   // and fails alike, so nobody waits for a peer
-  if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
+  if (!isBroadcast(algo))  // a broadcast does not use its op
+    if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
     std::vector<int> re;
@@ -132,9 +158,14 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
       re.assign(recv_elems, recv_elems + ctx->ctx->size);
     }
     if (algo == GLOO_HIP_ALGO_BCUBE && recv_elems) re.assign(recv_elems, recv_elems + 1);  // {base}
+    std::vector<void*> ps(ptrs, ptrs + nptrs);
+    if (isBroadcast(algo)) {
+      std::vector<int> order;
+      broadcastArgs(algo, ctx->ctx->size, recv_elems, nptrs, &re, &order, &op);
+      for (int i = 0; i < nptrs; i++) ps[i] = ptrs[order[i]];
+    }
     auto a = std::make_unique<gloo_hip_algorithm>();
-    a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype,
-                                                       std::vector<void*>(ptrs, ptrs + nptrs), count, re,
+    a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
                                                        static_cast<hipStream_t>(stream), std::vector<void*>{}, 0,
                                                        workspace);
     *out = a.release();
@@ -145,7 +176,8 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
                                       int nptrs, size_t count, const int* recv_elems,
                                       const gloo_hip_stream_t* streams, int nstreams, int workspace,
                                       gloo_hip_algorithm_t* out) {
-  if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
+  if (!isBroadcast(algo))
+    if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
     // gloo/cuda_allreduce_ring_chunked.cc:55-58
@@ -157,8 +189,15 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
       re.assign(recv_elems, recv_elems + ctx->ctx->size);
     }
     if (algo == GLOO_HIP_ALGO_BCUBE && recv_elems) re.assign(recv_elems, recv_elems + 1);  // {base}
+    std::vector<void*> ps(ptrs, ptrs + nptrs);
     std::vector<hipStream_t> ss;
     for (int i = 0; i < nstreams; i++) ss.push_back(static_cast<hipStream_t>(streams[i]));
+    if (isBroadcast(algo)) {  // stream i stays with pointer i
+      std::vector<int> order;
+      broadcastArgs(algo, ctx->ctx->size, recv_elems, nptrs, &re, &order, &op);
+      for (int i = 0; i < nptrs; i++) ps[i] = ptrs[order[i]];
+      for (int i = 0; i < nstreams; i++) ss[i] = static_cast<hipStream_t>(streams[order[i]]);
+    }
     // Validated before the collective construction: a refusal after it would
     // run the executor's release() on this rank alone, and the peers would
     // wait at its barrier until the context timeout.
@@ -166,8 +205,8 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
       GLOO_AMD_ENFORCE(t != nullptr || ss.size() == 1, "null stream in a list of ", ss.size(),
                        " (one stream per pointer)");
     auto a = std::make_unique<gloo_hip_algorithm>();
-    a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, std::vector<void*>(ptrs, ptrs + nptrs), count,
-                                             re, ss.empty() ? nullptr : ss[0], std::vector<void*>{}, 0, workspace);
+    a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
+                                             ss.empty() ? nullptr : ss[0], std::vector<void*>{}, 0, workspace);
     if (ss.size() > 1) a->exec->setStreams(ss);
     *out = a.release();
   });
@@ -282,6 +321,32 @@ int gloo_hip_reduce_to_root(gloo_hip_context_t ctx, const gloo_hip_reduce_option
     std::vector<void*> ins, outs{o->output};
     if (o->input && o->input != o->output) ins.push_back(o->input);  // :46-48
     runCached(ctx, GLOO_HIP_ALGO_REDUCE, o->op, o->dtype, ins, outs, o->elements, o->max_segment_bytes, o->tag,
+              o->stream, {o->root});
+  });
+}
+
+int gloo_hip_broadcast(gloo_hip_context_t ctx, const gloo_hip_broadcast_options_t* o) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && o, "null argument");
+    GLOO_AMD_ENFORCE(gloo_hip_dtype_size(o->dtype) > 0, "unknown dtype ", o->dtype);
+    GLOO_AMD_ENFORCE(o->root >= 0 && o->root < ctx->ctx->size, "broadcast: root rank ", o->root, " outside [0, ",
+                     ctx->ctx->size, ")");  // gloo/broadcast.cc:28
+    if (o->elements == 0) return;
+    GLOO_AMD_ENFORCE(o->output, "null output");
+    // A root with a separate input: its output takes the input's bytes on the
+    // call's stream first (the schedule depends on sizes only, and only the
+    // root knows of its input, so the cached executor is the same on every
+    // rank: one pointer, the output).
+    const bool separate = ctx->ctx->rank == o->root && o->input && o->input != o->output;
+    if (separate) {
+      hipStream_t s = static_cast<hipStream_t>(o->stream);
+      GLOO_AMD_HIP_CHECK(hipSetDevice(ctx->ctx->device()));
+      GLOO_AMD_HIP_CHECK(hipMemcpyAsync(o->output, o->input, o->elements * gloo_hip_dtype_size(o->dtype),
+                                        hipMemcpyDeviceToDevice, s));
+      // no stream given: the executor's own stream does not wait for the null stream
+      if (!s) GLOO_AMD_HIP_CHECK(hipStreamSynchronize(nullptr));
+    }
+    runCached(ctx, GLOO_HIP_ALGO_BROADCAST, GLOO_HIP_SUM, o->dtype, {}, {o->output}, o->elements, 0, o->tag,
               o->stream, {o->root});
   });
 }

@@ -98,6 +98,29 @@ bool broadcastsReceive(const std::vector<Step>& steps, size_t i, size_t nptrs) {
          b.kind == GLOO_HIP_STEP_LOCAL_BCAST && b.dst_off <= c.dst_off &&
          c.dst_off + c.length <= b.dst_off + b.length;
 }
+// The root's side of the broadcast plan (plan.cc planBroadcast) from step i:
+// (WAIT_NOTIFY(peer), SEND(whole range from pointer 0 to peer))+ and the
+// LOCAL_BCAST of that range, if any.  Returns the step after the run (i when
+// step i does not start one) and the SEND steps' indices.
+size_t fanoutRun(const std::vector<Step>& steps, size_t i, std::vector<size_t>* sends, bool* bcast) {
+  size_t j = i;
+  sends->clear();
+  *bcast = false;
+  while (j + 1 < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_NOTIFY && steps[j + 1].kind == GLOO_HIP_STEP_SEND &&
+         steps[j + 1].peer == steps[j].peer && steps[j + 1].flags == 0 && steps[j + 1].length > 0 &&
+         steps[j + 1].src_off == steps[i + 1].src_off && steps[j + 1].length == steps[i + 1].length) {
+    sends->push_back(j + 1);
+    j += 2;
+  }
+  if (sends->empty()) return i;
+  const Step& s0 = steps[(*sends)[0]];
+  if (j < steps.size() && steps[j].kind == GLOO_HIP_STEP_LOCAL_BCAST && steps[j].dst_off == s0.src_off &&
+      steps[j].length == s0.length) {
+    *bcast = true;
+    j++;
+  }
+  return j;
+}
 }  // namespace
 
 void markInterpBatches(InterpStep* v, size_t n, size_t es) {
@@ -538,7 +561,9 @@ void PlanExecutor::buildInterp() {
     return true;
   };
   // the pipelined halving-doubling's step pairs that run as one pass (enqueue())
-  const bool fuseLocal = planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED && !custom_ && !anyRemote_;
+  // (and the broadcast plan's receive + broadcast, the same pass)
+  const bool fuseLocal = (planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED || planAlgo_ == GLOO_HIP_ALGO_BROADCAST) &&
+                         !custom_ && !anyRemote_;
   std::vector<const char*> foldSrcs;
   const std::vector<Step>& steps = plan_.steps;
   for (size_t i = 0; i < steps.size(); i++) {
@@ -770,10 +795,57 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
   // The per-range local steps of the pipelined halving-doubling run in one
   // pass with their neighbour (below); custom ops, event profiling and
   // pointers on other GPUs of the process keep the plan's own steps.
-  const bool fuseLocal = planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED && deviceSignal_ && !custom_ &&
-                         !profiling_ && !anyRemote_;
+  // The broadcast plan's COPY + LOCAL_BCAST on a receiver is the same receive
+  // + broadcast pass.
+  const bool fuseLocal = (planAlgo_ == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED || planAlgo_ == GLOO_HIP_ALGO_BROADCAST) &&
+                         deviceSignal_ && !custom_ && !profiling_ && !anyRemote_;
+  // The broadcast root's sends and local broadcast read the same bytes: one
+  // pass over the source (launchFanout) behind one wait for every peer's
+  // clear-to-send.  Peers' inboxes first (their flags are published by the
+  // first launch), then the local pointers; kMaxCopyEntries destinations a
+  // launch, each launch with the ticket counter of its first peer's channel.
+  const bool fanout = planAlgo_ == GLOO_HIP_ALGO_BROADCAST && deviceSignal_ && !anyRemote_;
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
+    if (fanout && s.kind == GLOO_HIP_STEP_WAIT_NOTIFY) {
+      std::vector<size_t> sends;
+      bool withBcast = false;
+      const size_t next = fanoutRun(steps, i, &sends, &withBcast);
+      if (next != i) {
+        for (size_t b = 0; b < sends.size(); b += kMaxWaitEntries) {
+          std::vector<const uint64_t*> flags;
+          std::vector<Seq> targets;
+          for (size_t k = b; k < std::min(sends.size(), b + kMaxWaitEntries); k++) {
+            const Step& w = steps[sends[k] - 1];
+            flags.push_back(waitFlag(w.peer, w.slot));
+            targets.push_back(seqOf(sends[k] - 1, r, graph));
+          }
+          GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                             ctx_->errorWordDevicePtr(me), stream_));
+        }
+        const Step& s0 = steps[sends[0]];
+        const size_t off = s0.src_off * es_, bytes = s0.length * es_;
+        std::vector<FanoutDesc> dests;
+        std::vector<unsigned*> tickets;  // of each destination's channel (nullptr: local)
+        for (size_t k : sends) {
+          const Step& t = steps[k];
+          dests.push_back(FanoutDesc{sendDst(t), sigFlag(t.peer, t.slot), seqOf(k, r, graph)});
+          tickets.push_back(ticket_ + (size_t)t.peer * GLOO_HIP_NUM_SLOTS + t.slot);
+        }
+        for (size_t j = 1; withBcast && j < ptrs_.size(); j++) {
+          dests.push_back(FanoutDesc{userPtr(j) + off, nullptr, Seq{}});
+          tickets.push_back(nullptr);
+        }
+        for (size_t b = 0; b < dests.size(); b += kMaxCopyEntries) {
+          const int nd = (int)std::min<size_t>(kMaxCopyEntries, dests.size() - b);
+          checkRc(launchFanout(userPtr(0) + off, bytes, dests.data() + b, nd, tickets[b], epoch,
+                               fanoutGrid(bytes, kFanoutBlocks), stream_),
+                  "fanout_kernel");
+        }
+        i = next - 1;
+        continue;
+      }
+    }
     // Local fold + first send: LOCAL_REDUCE(R) then SEND(R) is one fold of
     // the k pointers that stores each tile to output 0 and into the peer's
     // inbox, its last workgroup publishing the arrival (fold + forward).

@@ -1208,6 +1208,49 @@ Plan planReduce(int rank, int size, uint64_t count, const NewStyleOptions& o) {
   return p;
 }
 
+// ---------------------------------------------------------------------------
+// CudaBroadcastOneToAll (gloo/cuda_broadcast_one_to_all.cc:87-156).  Pointer 0
+// is the root pointer (the C-ABI layer hands the executor the pointer list
+// with the root pointer first), so LOCAL_BCAST keeps its meaning on every
+// rank.  Root: per peer in ascending rank the peer's clear-to-send, then the
+// whole range into that peer's inbox (:106-112); the local broadcast while
+// the sends are in flight (:115-120); the send completions (:123-128).
+// Non-root: clear-to-send to the root, the arrival, the copy out of the
+// inbox into pointer 0, the local broadcast (:135-148).
+//
+// Runs need no barrier and no previous-run credit: the clear-to-send IS the
+// credit.  A receiver issues run r + 1's clear-to-send on its stream after
+// run r's COPY out of the inbox, and the root's run r + 1 SEND waits for it.
+// Arena = [inbox: count] on a non-root rank, nothing on the root.
+// ---------------------------------------------------------------------------
+Plan planBroadcast(int rank, int size, uint64_t count, int nptrs, int root) {
+  if (root < 0 || root >= size)                                         // GLOO_ENFORCE_GE / _LT, :30-31
+    throw std::invalid_argument("broadcast: root rank " + std::to_string(root) + " outside [0, " +
+                                std::to_string(size) + ")");
+  Plan p;
+  if (count == 0) return p;  // nothing to move: no data steps, and so no handshake to guard them
+  if (size > 1) {
+    if (rank == root) {
+      for (int peer = 0; peer < size; peer++) {                         // :106-112
+        if (peer == rank) continue;
+        p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, peer, GLOO_HIP_SLOT_NOTIFY));
+        p.steps.push_back(mk(GLOO_HIP_STEP_SEND, peer, GLOO_HIP_SLOT_DATA0, 0, 0, 0, count));
+      }
+    } else {
+      p.arena = count;
+      p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, root, GLOO_HIP_SLOT_DATA0, 0, 0, 0, count));
+      p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, root, GLOO_HIP_SLOT_NOTIFY));       // :135
+      p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, root, GLOO_HIP_SLOT_DATA0));     // :136
+      p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, 0, 0, count));  // :139
+    }
+  }
+  if (nptrs > 1) p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_BCAST, -1, 0, 0, 0, 0, count));  // :115-120, :142-148
+  if (size > 1 && rank == root)
+    for (int peer = 0; peer < size; peer++)                             // :123-128
+      if (peer != rank) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_SEND, peer, GLOO_HIP_SLOT_DATA0));
+  return p;
+}
+
 }  // namespace
 
 Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewStyleOptions& o) {
@@ -1238,6 +1281,10 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
     if (base == GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED)
       throw std::invalid_argument(
           "pipelined halving-doubling has no mesh form (GLOO_HIP_ALGO_MESH): it is an order of the reference's route");
+    // one hop from the root to every rank already: there is nothing to derive
+    if (base == GLOO_HIP_ALGO_BROADCAST)
+      throw std::invalid_argument("broadcast has no mesh form: algorithm " + std::to_string(algo) +
+                                  " (GLOO_HIP_ALGO_BROADCAST | GLOO_HIP_ALGO_MESH) is refused");
     if (base == GLOO_HIP_ALGO_REDUCE_SCATTER && (int)recvElems.size() != size)
       throw std::invalid_argument("recvElems must have size entries");
     return makeMeshPlan(base, rank, size, count, nptrs, recvElems);
@@ -1254,6 +1301,13 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
     case GLOO_HIP_ALGO_REDUCE_SCATTER:
       if ((int)recvElems.size() != size) throw std::invalid_argument("recvElems must have size entries");
       return planReduceScatter(rank, size, count, nptrs, recvElems);
+    case GLOO_HIP_ALGO_BROADCAST: {  // recvElems = {root, root pointer}, absent entries 0
+      const int rootPointer = recvElems.size() > 1 ? recvElems[1] : 0;
+      if (rootPointer < 0 || rootPointer >= nptrs)
+        throw std::invalid_argument("broadcast: root pointer " + std::to_string(rootPointer) + " outside [0, " +
+                                    std::to_string(nptrs) + ")");
+      return planBroadcast(rank, size, count, nptrs, recvElems.empty() ? 0 : recvElems[0]);
+    }
   }
   throw std::invalid_argument("unknown algorithm");
 }
@@ -1276,6 +1330,8 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
       re.assign(recv_elems, recv_elems + size);
     }
     if ((algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_BCUBE && recv_elems) re.assign(recv_elems, recv_elems + 1);  // {base}
+    if ((algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_BROADCAST && recv_elems)
+      re.assign(recv_elems, recv_elems + 2);  // {root, root pointer}
     gloo_amd::Plan p;
     if (gloo_amd::isNewStyle(algo)) {
       gloo_amd::NewStyleOptions o;

@@ -1188,6 +1188,89 @@ __global__ __launch_bounds__(kCopyBlock) void copy_signal_kernel(CopyList L, con
 }
 
 // ---------------------------------------------------------------------------
+// One source, many destinations (signal.h launchFanout): the root's side of
+// GLOO_HIP_ALGO_BROADCAST, its SENDs into every peer's inbox and the
+// LOCAL_BCAST to its other pointers, which all read the same bytes.  Bytes
+// only: no dtype, no op.  A capped grid walks 16 KiB tiles of the SOURCE
+// (512 lanes x 2 x 16 B, aligned loads from the source's first 16-B
+// boundary, `nt`); each tile is loaded once and stored to every destination
+// at that destination's own misalignment (descriptor at its aligned-down
+// address, the byte offset in soffset, as fold_send_kernel's forwards):
+// write-through into a peer's inbox (an entry with a flag), plain into a
+// local pointer (the caller reads it next).  The source's head up to its
+// boundary and the ragged tail (< 16 bytes each) go byte-wise from block 0.
+// Completion as copy_signal_kernel: every wave drains, the workgroup syncs,
+// block 0 releases its plain edge bytes, one lane takes a ticket; the
+// workgroup holding the launch's last ticket resets the counter and
+// publishes every entry's flag.
+// ---------------------------------------------------------------------------
+struct FanoutList {
+  int n;
+  char* dst[kMaxCopyEntries];
+  uint64_t* flag[kMaxCopyEntries];  // nullptr: a local destination (plain stores, nobody to tell)
+  Seq seq[kMaxCopyEntries];
+  unsigned* ticket;                 // zero between launches; nullptr: no entry has a flag
+};
+
+__global__ __launch_bounds__(kCopyBlock) void fanout_kernel(const char* src, size_t bytes, FanoutList F,
+                                                            const uint64_t* epoch) {
+  const size_t mis = (16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15;
+  const size_t head = mis < bytes ? mis : bytes;
+  const size_t nvec = (bytes - head) / 16;
+  const size_t tail0 = head + nvec * 16;
+  if (blockIdx.x == 0) {
+    const size_t t = threadIdx.x;  // head < 16 and bytes - tail0 < 16: one lane per edge byte
+    if (t < head || (t >= 16 && tail0 + (t - 16) < bytes)) {
+      const size_t i = t < head ? t : tail0 + (t - 16);
+      const char c = src[i];
+      for (int r = 0; r < F.n; r++) F.dst[r][i] = c;
+    }
+  }
+  constexpr uint32_t kTileBytes = kCopyBlock * kCopyUnroll * 16;
+  const size_t body = nvec * 16;
+  const uint32_t lane_off = threadIdx.x * 16u;
+  for (size_t base = (size_t)blockIdx.x * kTileBytes; base < body; base += (size_t)gridDim.x * kTileBytes) {
+    const uint32_t n = (uint32_t)((body - base) < kTileBytes ? (body - base) : kTileBytes);
+    const auto rs = make_rsrc(src + head + base, n);
+    u32x4 v[kCopyUnroll];
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; u++) v[u] = bload<kAuxNT>(rs, lane_off + u * kCopyBlock * 16);
+    for (int r = 0; r < F.n; r++) {
+      const Src dr = src_of(F.dst[r] + head);
+      const auto rd = make_rsrc(dr.base + base, n + dr.mis);
+      if (F.flag[r]) {
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) bstore<kAuxWT>(rd, lane_off + u * kCopyBlock * 16, v[u], dr.mis);
+      } else {
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) bstore<0>(rd, lane_off + u * kCopyBlock * 16, v[u], dr.mis);
+      }
+    }
+  }
+  if (!F.ticket) return;  // local destinations only
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // the bodies into the inboxes went out write-through and every wave has
+    // waited for them; only block 0, whose edge bytes are plain stores,
+    // releases before its ticket
+    if (blockIdx.x == 0 && (head || tail0 < bytes)) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const uint64_t ep = epoch ? *epoch : 0;
+    const unsigned t = __hip_atomic_fetch_add(F.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == gridDim.x - 1) {
+      __hip_atomic_store(F.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      for (int r = 0; r < F.n; r++)
+        if (F.flag[r])
+          __hip_atomic_store(F.flag[r], F.seq[r].base + ep * F.seq[r].perRun, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side dispatch.
 // ---------------------------------------------------------------------------
 int g_variant = 0;  // fp32 SUM kernel variant (measurement knob)
@@ -1543,6 +1626,28 @@ int launchCopySignal(void* dst, const void* src, size_t bytes, uint64_t* flag, S
   return launchCopySignalMulti(&d, 1, epoch, s);
 }
 
+unsigned fanoutGrid(size_t bytes, unsigned maxBlocks) { return copySignalGrid(bytes, maxBlocks); }
+
+int launchFanout(const void* src, size_t bytes, const FanoutDesc* d, int n, unsigned* ticket, const uint64_t* epoch,
+                 unsigned grid, hipStream_t s) {
+  if (n < 1 || n > kMaxCopyEntries || grid == 0) return set_error(GLOO_HIP_EINVAL_ARG, "fan-out list size out of range");
+  FanoutList F;
+  memset(&F, 0, sizeof(F));
+  F.n = n;
+  bool flagged = false;
+  for (int j = 0; j < n; j++) {
+    if (!d[j].dst) return set_error(GLOO_HIP_EINVAL_PTR, "null fan-out destination");
+    F.dst[j] = static_cast<char*>(d[j].dst);
+    F.flag[j] = d[j].flag;
+    F.seq[j] = d[j].seq;
+    flagged = flagged || d[j].flag;
+  }
+  if (flagged && !ticket) return set_error(GLOO_HIP_EINVAL_ARG, "a signalled fan-out needs a ticket counter");
+  F.ticket = flagged ? ticket : nullptr;
+  fanout_kernel<<<grid, kCopyBlock, 0, s>>>(static_cast<const char*>(src), bytes, F, epoch);
+  return check_launch("fanout_kernel");
+}
+
 struct CustomEntry {
   gloo_hip_custom_fn fn;
   void* user;
@@ -1790,6 +1895,18 @@ int gloo_hip_copy_kernel_multi(void* const* dsts, const void* const* srcs, const
   }
   if (m == 0) return GLOO_HIP_OK;
   return launchCopySignalMulti(d, m, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int gloo_hip_fanout_kernel(void* const* dsts, int n, const void* src, size_t bytes, unsigned blocks,
+                           gloo_hip_stream_t stream) {
+  if (n < 1 || n > gloo_amd::kMaxCopyEntries || !dsts) return set_error(GLOO_HIP_EINVAL_ARG, "1..8 destinations");
+  if (bytes == 0) return GLOO_HIP_OK;
+  if (!src) return set_error(GLOO_HIP_EINVAL_PTR, "null pointer");
+  gloo_amd::FanoutDesc d[gloo_amd::kMaxCopyEntries];
+  for (int j = 0; j < n; j++) d[j] = gloo_amd::FanoutDesc{dsts[j], nullptr, gloo_amd::Seq{}};
+  return gloo_amd::launchFanout(src, bytes, d, n, nullptr, nullptr,
+                                gloo_amd::fanoutGrid(bytes, blocks ? blocks : gloo_amd::kFanoutBlocks),
+                                static_cast<hipStream_t>(stream));
 }
 
 int gloo_hip_register_op(gloo_hip_custom_fn fn, void* user, int* op_out) {

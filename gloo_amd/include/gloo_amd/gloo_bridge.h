@@ -366,4 +366,43 @@ class HipReduceScatterHalvingDoubling : public HipPlanAlgorithm<T, GLOO_HIP_ALGO
   }
 };
 
+// gloo::CudaBroadcastOneToAll (gloo/cuda_broadcast_one_to_all.h:20-31), the
+// reference constructor's argument order: after run() every pointer of every
+// rank holds the bytes of rank rootRank's ptrs[rootPointerRank]
+// (GLOO_HIP_ALGO_BROADCAST; there is no reduction function).
+template <typename T, typename W = HipDeviceWorkspace<T>>
+class HipBroadcastOneToAll : public Algorithm {
+ public:
+  HipBroadcastOneToAll(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, int count,
+                       int rootRank = 0, int rootPointerRank = 0,
+                       const std::vector<hipStream_t>& streams = std::vector<hipStream_t>())
+      : Algorithm(context) {
+    GLOO_ENFORCE(!ptrs.empty(), "need at least one pointer");
+    GLOO_ENFORCE_GE(rootRank, 0);  // gloo/cuda_broadcast_one_to_all.cc:30-31
+    GLOO_ENFORCE_LT(rootRank, context->size);
+    GLOO_ENFORCE(rootPointerRank >= 0 && rootPointerRank < (int)ptrs.size(), "invalid root pointer ", rootPointerRank);
+    GLOO_ENFORCE(streams.empty() || streams.size() == ptrs.size(), "one stream per pointer, or none");  // :35
+    boot_.reset(new hip_bridge::BootstrapContext(context, hip_bridge::deviceOf(ptrs[0])));
+    std::vector<void*> p(ptrs.begin(), ptrs.end());
+    std::vector<gloo_hip_stream_t> s(streams.begin(), streams.end());
+    const int re[2] = {rootRank, rootPointerRank};
+    hip_bridge::check(
+        gloo_hip_algorithm_create_streams(boot_->handle(), GLOO_HIP_ALGO_BROADCAST, 0 /* op: not used */,
+                                          hip_bridge::DType<T>::value, p.data(), (int)p.size(),
+                                          (size_t)(count > 0 ? count : 0), re, s.empty() ? nullptr : s.data(),
+                                          (int)s.size(), W::kind, &algo_),
+        "gloo_hip_algorithm_create");
+  }
+
+  ~HipBroadcastOneToAll() override {
+    if (algo_) (void)gloo_hip_algorithm_destroy(algo_);  // collective: a tear-down barrier
+  }
+
+  void run() override { hip_bridge::check(gloo_hip_algorithm_run(algo_), "run"); }
+
+ protected:
+  std::unique_ptr<hip_bridge::BootstrapContext> boot_;
+  gloo_hip_algorithm_t algo_ = nullptr;
+};
+
 }  // namespace gloo

@@ -9,6 +9,10 @@
 //        gloo/allreduce.cc:97-145)  ->  gloo::hip::allreduce(opts[, stream])
 //   gloo::reduce(gloo::ReduceOptions&)               (gloo/reduce.h:19-110,
 //        gloo/reduce.cc:21-247)     ->  gloo::hip::reduce(opts[, stream])
+//   gloo::broadcast(gloo::BroadcastOptions&)         (gloo/broadcast.h:16-89,
+//        gloo/broadcast.cc:16-95)   ->  gloo::hip::broadcast(opts[, stream])
+//        (bytes only: no reduce function; one-to-all from the root instead of
+//        the reference's binomial tree, the same bytes on every rank)
 //
 // The caller fills the SAME option object it would hand to gloo::allreduce /
 // gloo::reduce: setInput(s) / setOutput(s) with DEVICE pointers (the
@@ -45,6 +49,7 @@
 #include <vector>
 
 #include "gloo/allreduce.h"
+#include "gloo/broadcast.h"
 #include "gloo/math.h"
 #include "gloo/reduce.h"
 #include "gloo_amd/gloo_bridge.h"
@@ -169,6 +174,22 @@ struct ReduceAccess : ::gloo::ReduceOptions {
   static size_t get_maxSegmentSize(const ::gloo::ReduceOptions& o) { return o.*(&ReduceAccess::maxSegmentSize); }
 };
 
+struct BroadcastAccess : ::gloo::BroadcastOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::BroadcastOptions& o) {
+    return o.*(&BroadcastAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::BroadcastOptions& o) {
+    return o.*(&BroadcastAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::BroadcastOptions& o) {
+    return o.*(&BroadcastAccess::out);
+  }
+  static size_t get_elements(const ::gloo::BroadcastOptions& o) { return o.*(&BroadcastAccess::elements); }
+  static size_t get_elementSize(const ::gloo::BroadcastOptions& o) { return o.*(&BroadcastAccess::elementSize); }
+  static int get_root(const ::gloo::BroadcastOptions& o) { return o.*(&BroadcastAccess::root); }
+  static uint32_t get_tag(const ::gloo::BroadcastOptions& o) { return o.*(&BroadcastAccess::tag); }
+};
+
 }  // namespace detail
 
 // A CUSTOM reduce function for the new-style calls: `host` is what the
@@ -249,6 +270,34 @@ inline void reduce(::gloo::ReduceOptions& opts, hipStream_t stream = nullptr) {
   r.tag = A::get_tag(opts);
   r.stream = stream;
   ::gloo::hip_bridge::check(gloo_hip_reduce_to_root(ctx, &r), "gloo::hip::reduce");
+}
+
+// gloo::broadcast(opts) (gloo/broadcast.cc:16-95) on device buffers: every
+// rank's output receives the bytes of the root's input (of its output, when
+// it set none).  The options carry an element size and no type, and a
+// broadcast moves bytes, so the call goes down as elements * elementSize
+// elements of uint8.
+inline void broadcast(::gloo::BroadcastOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::BroadcastAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");
+  const int root = A::get_root(opts);
+  GLOO_ENFORCE(root >= 0 && root < ctxp->size, "invalid root ", root);  // gloo/broadcast.cc:28
+  const size_t bytes = A::get_elements(opts) * A::get_elementSize(opts);
+  void* out = A::get_out(opts)->ptr;
+  const bool isRoot = ctxp->rank == root;
+  GLOO_ENFORCE(isRoot || !A::get_in(opts), "Non-root may not specify input");  // gloo/broadcast.cc:38
+  if (bytes == 0) return;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, out);
+  gloo_hip_broadcast_options_t b;
+  b.dtype = GLOO_HIP_U8;
+  b.input = isRoot && A::get_in(opts) ? A::get_in(opts)->ptr : nullptr;
+  b.output = out;
+  b.elements = bytes;
+  b.root = root;
+  b.tag = A::get_tag(opts);
+  b.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_broadcast(ctx, &b), "gloo::hip::broadcast");
 }
 
 // Collective: tears down the library context (and its cached schedules)

@@ -344,4 +344,86 @@ inline void reduce(const ReduceOptions& o) {
   exec.run();
 }
 
+// CudaBroadcastOneToAll (gloo/cuda_broadcast_one_to_all.h:20-31): after run()
+// every pointer of every rank holds the bytes of the root rank's
+// ptrs[rootPointerRank].  GLOO_HIP_ALGO_BROADCAST: the executor gets the
+// pointers (and their streams) with the root pointer first, as the C-ABI
+// entry points hand them over.  No reduction function: a broadcast has none.
+template <typename T, typename W = HipDeviceWorkspace<T>>
+class HipBroadcastOneToAll : public Algorithm {
+ public:
+  HipBroadcastOneToAll(const std::shared_ptr<Context>& context, const std::vector<T*>& ptrs, int count,
+                       int rootRank = 0, int rootPointerRank = 0, const std::vector<hipStream_t>& streams = {})
+      : Algorithm(context) {
+    GLOO_AMD_ENFORCE(rootRank >= 0 && rootRank < context->size, "broadcast: root rank ", rootRank, " outside [0, ",
+                     context->size, ")");  // .cc:30-31
+    GLOO_AMD_ENFORCE(rootPointerRank >= 0 && rootPointerRank < (int)ptrs.size(), "broadcast: root pointer ",
+                     rootPointerRank, " outside [0, ", ptrs.size(), ")");
+    GLOO_AMD_ENFORCE(streams.empty() || streams.size() == ptrs.size(), "one stream per pointer, or none");  // .cc:35
+    std::vector<void*> p{ptrs[rootPointerRank]};
+    std::vector<hipStream_t> s;
+    if (!streams.empty()) s.push_back(streams[rootPointerRank]);
+    for (size_t i = 0; i < ptrs.size(); i++) {
+      if ((int)i == rootPointerRank) continue;
+      p.push_back(ptrs[i]);
+      if (!streams.empty()) s.push_back(streams[i]);
+    }
+    exec_ = PlanExecutor::create(context, GLOO_HIP_ALGO_BROADCAST, GLOO_HIP_SUM /* not used */, DType<T>::value, p,
+                                 static_cast<size_t>(count), std::vector<int>{rootRank}, s.empty() ? nullptr : s[0],
+                                 std::vector<void*>{}, 0, W::kind);
+    if (s.size() > 1) exec_->setStreams(s);
+  }
+  void run() override { exec_->run(); }
+
+ protected:
+  std::unique_ptr<PlanExecutor> exec_;
+};
+
+// gloo::BroadcastOptions (gloo/broadcast.h:16-87) over device pointers.
+class BroadcastOptions {
+ public:
+  explicit BroadcastOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInput(T* ptr, size_t elements) {
+    input_ = ptr;
+    elements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, size_t elements) {
+    output_ = ptr;
+    elements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  void setRoot(int root) { root_ = root; }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  void* input_ = nullptr;  // the root's only; null: the output is the input
+  void* output_ = nullptr;
+  size_t elements_ = 0;
+  int dtype_ = GLOO_HIP_U8;
+  int root_ = -1;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+
+// gloo::broadcast(opts) (gloo/broadcast.cc:16-95).  The reference walks a
+// binomial tree over its pairs; here the root sends to every rank itself
+// (GLOO_HIP_ALGO_BROADCAST: a root GPU has a direct link to every peer), and
+// the bytes that arrive are the same.  A root with a separate input runs with
+// the pointers {input, output}: its output is filled in the pass that sends.
+inline void broadcast(const BroadcastOptions& o) {
+  GLOO_AMD_ENFORCE(o.root_ >= 0 && o.root_ < o.context_->size, "broadcast: root rank ", o.root_, " outside [0, ",
+                   o.context_->size, ")");
+  if (o.elements_ == 0) return;
+  std::vector<void*> ptrs;
+  if (o.context_->rank == o.root_ && o.input_ && o.input_ != o.output_) ptrs.push_back(o.input_);
+  ptrs.push_back(o.output_);
+  PlanExecutor exec(o.context_, GLOO_HIP_ALGO_BROADCAST, GLOO_HIP_SUM /* not used */, o.dtype_, ptrs, o.elements_,
+                    {o.root_}, o.stream_);
+  exec.run();
+}
+
 }  // namespace gloo_amd

@@ -85,6 +85,23 @@ enum CopyStore { kCopyStoreNT = 0, kCopyStoreWT = 1, kCopyStorePlain = 2 };
 int launchCopySignalMulti(const CopyDesc* d, int n, const uint64_t* epoch, hipStream_t stream,
                           CopyStore localStore = kCopyStoreNT);
 
+// One source to up to kMaxCopyEntries destinations in ONE pass (reduce.hip
+// fanout_kernel): every 16 KiB tile of src is loaded once and stored to every
+// d[j].dst at its own 16-byte misalignment.  An entry with a flag is a peer's
+// inbox: write-through stores, and the workgroup taking the launch's last
+// ticket publishes *flag = seq (as launchCopySignal); an entry without one
+// is a local pointer: plain stores.  `ticket`: zero between launches, needed
+// when any entry has a flag.  Bytes only (no dtype, no op).
+struct FanoutDesc {
+  void* dst;
+  uint64_t* flag;
+  Seq seq;
+};
+constexpr unsigned kFanoutBlocks = 256;  // workgroups at most (fanoutGrid)
+unsigned fanoutGrid(size_t bytes, unsigned maxBlocks);
+int launchFanout(const void* src, size_t bytes, const FanoutDesc* d, int n, unsigned* ticket, const uint64_t* epoch,
+                 unsigned grid, hipStream_t stream);
+
 // Wait for several flags in one launch (one lane per flag), then ONE
 // system-scope acquire.  n <= kMaxWaitEntries.
 constexpr int kMaxWaitEntries = 16;

@@ -194,6 +194,15 @@ int gloo_hip_copy_kernel(void* dst, const void* src, size_t bytes, unsigned bloc
 int gloo_hip_copy_kernel_multi(void* const* dsts, const void* const* srcs, const size_t* bytes, int n,
                                unsigned blocks, gloo_hip_stream_t stream);
 
+/* (new, measurement) One source to up to 8 local destinations in ONE pass:
+ * each 16 KiB tile of src is loaded once and stored to every dsts[j] at that
+ * destination's own 16-byte misalignment (the root's fan-out of
+ * GLOO_HIP_ALGO_BROADCAST without its flags; tools/bcast_bench.py compares it
+ * with gloo_hip_copy_kernel_multi, which reads the source once per copy).
+ * blocks: workgroups (0: one per tile, capped at 256). */
+int gloo_hip_fanout_kernel(void* const* dsts, int n, const void* src, size_t bytes, unsigned blocks,
+                           gloo_hip_stream_t stream);
+
 /* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
  * is defined for (SUM..MIN on all twelve, BAND / BOR / BXOR on the six integer
  * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
@@ -272,6 +281,31 @@ typedef enum {
    * neighbour in one pass (local fold + first send, local fold + first
    * receive-reduce, receive + broadcast; executor_run.cc). */
   GLOO_HIP_ALGO_HALVING_DOUBLING_PIPELINED = 11,
+  /* CudaBroadcastOneToAll (gloo/cuda_broadcast_one_to_all.{h,cc}): after a
+   * run every pointer of every rank holds, byte for byte, what the root
+   * rank's root pointer held.  Not a reduction:
+   *   op     is NOT USED.  Any value is accepted (0, a pair the reductions
+   *          refuse such as BXOR with F32): no refusal looks at it.
+   *   dtype  gives the element size only; all twelve are valid.
+   *   recv_elems, when not NULL, points to TWO ints {root rank, root pointer
+   *          rank}; NULL means {0, 0} (the front ends pad an absent second
+   *          entry with 0).  This is how GLOO_HIP_ALGO_REDUCE passes its root.
+   *          A root outside [0, size), a root pointer outside [0, nptrs) and
+   *          | GLOO_HIP_ALGO_MESH are refused with GLOO_HIP_EINVAL_ARG; the
+   *          last-error text names the value.
+   * Order (the reference's, .cc:87-156).  Root: for each peer in ascending
+   * rank WAIT_NOTIFY (its clear-to-send) then SEND of the whole range; then
+   * LOCAL_BCAST when nptrs > 1; then WAIT_SEND per peer.  Non-root: DECL_RECV,
+   * NOTIFY (clear-to-send), WAIT_RECV, COPY inbox -> pointer 0, LOCAL_BCAST
+   * when nptrs > 1.  In a plan pointer 0 IS the root pointer: the algorithm
+   * entry points hand the executor the pointer list with it first.  One rank:
+   * the LOCAL_BCAST alone; count 0, or one rank with one pointer: no steps.
+   * The clear-to-send orders the root's next send after the receiver's copy
+   * out of its inbox, so runs need no barrier.  The executor never promotes
+   * this plan to another route; it runs the root's sends and local broadcast
+   * as one pass over the source (reduce.hip fanout_kernel) and the receiver's
+   * COPY + LOCAL_BCAST as one pass over the inbox. */
+  GLOO_HIP_ALGO_BROADCAST = 12,
 } gloo_hip_algo_t;
 
 /* algo | GLOO_HIP_ALGO_MESH: the algorithm's result with mesh data movement,
@@ -500,7 +534,7 @@ int gloo_hip_algorithm_stats(gloo_hip_algorithm_t algo, double* stats4);
  * abandoned, gloo_hip_last_error() says why. */
 int gloo_hip_algorithm_mode(gloo_hip_algorithm_t algo, int* mode4);
 /* The same for the schedule that ran the latest function-style call
- * (gloo_hip_allreduce / gloo_hip_reduce_to_root) on `ctx`. */
+ * (gloo_hip_allreduce / gloo_hip_reduce_to_root / gloo_hip_broadcast) on `ctx`. */
 int gloo_hip_context_mode(gloo_hip_context_t ctx, int* mode4);
 
 /* ------------------------------------------------------------------------
@@ -552,6 +586,30 @@ typedef struct {
 } gloo_hip_reduce_options_t;
 
 int gloo_hip_reduce_to_root(gloo_hip_context_t ctx, const gloo_hip_reduce_options_t* opts);
+
+/* ------------------------------------------------------------------------
+ * New-style function API: gloo::broadcast(BroadcastOptions&)
+ * (gloo/broadcast.h:16-89, gloo/broadcast.cc): afterwards `output` on every
+ * rank holds the bytes of the root's `input` (the root's `output` when its
+ * input is NULL or the same pointer).  The reference walks a binomial tree
+ * over its pairs; this runs the one-to-all route of CudaBroadcastOneToAll
+ * (GLOO_HIP_ALGO_BROADCAST), because a root GPU has a direct link to every
+ * peer and the bytes that arrive are the same.  A root with a separate input
+ * first copies it to its output on the call's stream.  Collective, cached per
+ * option set (dtype, elements, root, tag) like gloo_hip_allreduce;
+ * gloo_hip_context_mode reports the schedule that ran.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int dtype;                /* gloo_hip_dtype_t: setInput<T>/setOutput<T>            */
+  void* input;              /* device pointer; used on the root only; NULL: the output is the input */
+  void* output;             /* device pointer                                        */
+  size_t elements;
+  int root;                 /* setRoot                                               */
+  uint32_t tag;             /* setTag                                                */
+  gloo_hip_stream_t stream; /* NULL: the output is complete on return                */
+} gloo_hip_broadcast_options_t;
+
+int gloo_hip_broadcast(gloo_hip_context_t ctx, const gloo_hip_broadcast_options_t* opts);
 
 /* ------------------------------------------------------------------------
  * The xGMI transport: bound buffers of gloo::transport::Pair / Buffer
