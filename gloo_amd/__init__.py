@@ -59,7 +59,7 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
             "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
-            "gloo_hip_fanout_kernel")
+            "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel")
 
 
 class GlooHipError(RuntimeError):
@@ -94,6 +94,8 @@ def _load():
     L.gloo_hip_copy_kernel_multi.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int,
                                              ctypes.c_uint, vp]
     L.gloo_hip_fanout_kernel.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, sz, ctypes.c_uint, vp]
+    L.gloo_hip_gather_fanout_kernel.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, sz,
+                                                ctypes.c_uint, vp]
     return L
 
 
@@ -186,6 +188,15 @@ def fanout_kernel(dsts, src, nbytes, blocks=0, stream=0):
     _check(lib.gloo_hip_fanout_kernel((ctypes.c_void_p * n)(*dsts), n, src, nbytes, blocks, stream or None))
 
 
+def gather_fanout_kernel(dsts, srcs, nbytes, blocks=0, stream=0):
+    """gloo_hip_gather_fanout_kernel: up to 8 sources of nbytes each, laid
+    side by side (source i at dst + i * nbytes) in up to 8 destinations, in
+    one pass (the allgather sender's pass without its flags)."""
+    n, k = len(dsts), len(srcs)
+    _check(lib.gloo_hip_gather_fanout_kernel((ctypes.c_void_p * n)(*dsts), n, (ctypes.c_void_p * k)(*srcs), k, nbytes,
+                                             blocks, stream or None))
+
+
 def set_variant(v):
     """Measurement knob: fp32 SUM kernel variant (0 = tuned default)."""
     return lib.gloo_hip_set_variant(int(v))
@@ -273,7 +284,10 @@ ALGORITHMS = {"ring_chunked": 0, "halving_doubling": 1, "ring": 2, "local": 3,
               "halving_doubling_pipelined": 11,
               # CudaBroadcastOneToAll (GLOO_HIP_ALGO_BROADCAST): recv_elems = [root, root pointer];
               # `op` is not used
-              "broadcast": 12}
+              "broadcast": 12,
+              # AllgatherRing / gloo::allgather (GLOO_HIP_ALGO_ALLGATHER): ptrs = [out, in_0 ... in_{k-1}]
+              # ([out]: in place), count elements per input; `op` is not used
+              "allgather": 13}
 
 
 def _bind_collectives(L):
@@ -417,7 +431,7 @@ class Context:
 
     def last_mode(self):
         """How the latest function-style call (allreduce / reduce_to_root /
-        broadcast) on this context ran (see Algorithm.mode)."""
+        broadcast / allgather) on this context ran (see Algorithm.mode)."""
         out = (ctypes.c_int * 4)()
         _check(lib.gloo_hip_context_mode(self._h, out))
         return _mode_dict(out)
@@ -620,3 +634,37 @@ def broadcast(ctx, output, elements, dtype, root, input=None, tag=0, stream=0):
     o.tag = tag
     o.stream = stream or None
     _check(lib.gloo_hip_broadcast(ctx._h, ctypes.byref(o)))
+
+
+# ---- new-style function API: gloo::allgather(opts) / gloo::allgatherv(opts) --
+
+class AllgatherOptions(ctypes.Structure):
+    """gloo_hip_allgather_options_t (mirrors gloo::AllgatherOptions, gloo/allgather.h, and
+    gloo::AllgathervOptions, gloo/allgatherv.h)."""
+    _fields_ = [("dtype", ctypes.c_int), ("input", ctypes.c_void_p), ("output", ctypes.c_void_p),
+                ("elements", ctypes.c_size_t), ("counts", ctypes.POINTER(ctypes.c_size_t)),
+                ("tag", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
+lib.gloo_hip_allgather.argtypes = [ctypes.c_void_p, ctypes.POINTER(AllgatherOptions)]
+EXPORTED = EXPORTED + ("gloo_hip_allgather",)
+
+
+def allgather(ctx, output, elements, dtype, input=None, counts=None, tag=0, stream=0):
+    """gloo::allgather(opts) / gloo::allgatherv(opts) on device pointers
+    (GLOO_HIP_ALGO_ALLGATHER): afterwards every rank's output holds rank 0's
+    input, rank 1's input, ... back to back, `elements` each, or counts[r]
+    with counts (one entry per rank; elements is then ignored).  input None:
+    in place, the rank's own block already sits in its slot of the output."""
+    o = AllgatherOptions()
+    o.dtype = _as_dtype(dtype)
+    o.input = input or None
+    o.output = output
+    o.elements = int(elements)
+    arr = None
+    if counts is not None:
+        arr = (ctypes.c_size_t * len(counts))(*[int(c) for c in counts])
+        o.counts = ctypes.cast(arr, ctypes.POINTER(ctypes.c_size_t))
+    o.tag = tag
+    o.stream = stream or None
+    _check(lib.gloo_hip_allgather(ctx._h, ctypes.byref(o)))

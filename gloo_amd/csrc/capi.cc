@@ -1,5 +1,6 @@
 // capi.cc — C-ABI over Context / PlanExecutor; no exception crosses it.
 #include <chrono>
+#include <cstdint>
 #include <cstring>
 #include <list>
 #include <memory>
@@ -108,6 +109,20 @@ void broadcastArgs(int algo, int size, const int* recv_elems, int nptrs, std::ve
     if (i != rootPointer) order->push_back(i);
   *op = GLOO_HIP_SUM;
 }
+
+// GLOO_HIP_ALGO_ALLGATHER at the algorithm entry points: ptrs = {out, in_0 ...
+// in_{k-1}} (nptrs = 1: in place), `count` elements per input on every rank,
+// recv_elems NULL.  | GLOO_HIP_ALGO_MESH is refused here, before any exchange
+// with a peer.  `op` is not used; the executor gets SUM, which every dtype has.
+void allgatherArgs(int algo, void* const* ptrs, int nptrs, const int* recv_elems, std::vector<void*>* outs,
+                   std::vector<void*>* ins, int* op) {
+  GLOO_AMD_ENFORCE(!(algo & GLOO_HIP_ALGO_MESH), "allgather has no mesh form: algorithm ", algo,
+                   " (GLOO_HIP_ALGO_ALLGATHER | GLOO_HIP_ALGO_MESH) is refused");
+  GLOO_AMD_ENFORCE(!recv_elems, "allgather: recv_elems must be NULL (per-rank counts: gloo_hip_allgather)");
+  outs->assign(1, ptrs[0]);
+  ins->assign(ptrs + 1, ptrs + nptrs);
+  *op = GLOO_HIP_SUM;
+}
 }  // namespace
 
 extern "C" {
@@ -148,7 +163,7 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
                                  gloo_hip_algorithm_t* out) {
   // refused on this rank before any exchange: every rank makes the same call
   // and fails alike, so nobody waits for a peer
-  if (!isBroadcast(algo))  // a broadcast does not use its op
+  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo))  // a broadcast / an allgather does not use its op
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
@@ -164,10 +179,11 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
       broadcastArgs(algo, ctx->ctx->size, recv_elems, nptrs, &re, &order, &op);
       for (int i = 0; i < nptrs; i++) ps[i] = ptrs[order[i]];
     }
+    std::vector<void*> ins;
+    if (gloo_amd::isAllgather(algo)) allgatherArgs(algo, ptrs, nptrs, recv_elems, &ps, &ins, &op);
     auto a = std::make_unique<gloo_hip_algorithm>();
     a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
-                                                       static_cast<hipStream_t>(stream), std::vector<void*>{}, 0,
-                                                       workspace);
+                                                       static_cast<hipStream_t>(stream), ins, 0, workspace);
     *out = a.release();
   });
 }
@@ -176,7 +192,7 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
                                       int nptrs, size_t count, const int* recv_elems,
                                       const gloo_hip_stream_t* streams, int nstreams, int workspace,
                                       gloo_hip_algorithm_t* out) {
-  if (!isBroadcast(algo))
+  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo))
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
@@ -204,9 +220,11 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
     for (hipStream_t t : ss)
       GLOO_AMD_ENFORCE(t != nullptr || ss.size() == 1, "null stream in a list of ", ss.size(),
                        " (one stream per pointer)");
+    std::vector<void*> ins;  // an allgather: stream i stays with pointer i of {out, in_0 ...}
+    if (gloo_amd::isAllgather(algo)) allgatherArgs(algo, ptrs, nptrs, recv_elems, &ps, &ins, &op);
     auto a = std::make_unique<gloo_hip_algorithm>();
     a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
-                                             ss.empty() ? nullptr : ss[0], std::vector<void*>{}, 0, workspace);
+                                             ss.empty() ? nullptr : ss[0], ins, 0, workspace);
     if (ss.size() > 1) a->exec->setStreams(ss);
     *out = a.release();
   });
@@ -348,6 +366,32 @@ int gloo_hip_broadcast(gloo_hip_context_t ctx, const gloo_hip_broadcast_options_
     }
     runCached(ctx, GLOO_HIP_ALGO_BROADCAST, GLOO_HIP_SUM, o->dtype, {}, {o->output}, o->elements, 0, o->tag,
               o->stream, {o->root});
+  });
+}
+
+int gloo_hip_allgather(gloo_hip_context_t ctx, const gloo_hip_allgather_options_t* o) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && o, "null argument");
+    GLOO_AMD_ENFORCE(gloo_hip_dtype_size(o->dtype) > 0, "unknown dtype ", o->dtype);
+    const int P = ctx->ctx->size;
+    // the per-rank counts go down as the plan's recv_elems (ints); none: `elements` everywhere
+    std::vector<int> counts;
+    size_t total = 0;
+    for (int q = 0; o->counts && q < P; q++) {
+      GLOO_AMD_ENFORCE(o->counts[q] <= (size_t)INT32_MAX, "allgather: count ", o->counts[q], " of rank ", q,
+                       " is too large");
+      counts.push_back((int)o->counts[q]);
+      total += o->counts[q];
+    }
+    if (!o->counts) total = o->elements * (size_t)P;
+    if (total == 0) return;
+    GLOO_AMD_ENFORCE(o->output, "null output");
+    // in place or not is part of the cached schedule's key (the plan's
+    // exchange does not depend on it: a block is one input either way)
+    std::vector<void*> ins;
+    if (o->input) ins.push_back(o->input);
+    runCached(ctx, GLOO_HIP_ALGO_ALLGATHER, GLOO_HIP_SUM, o->dtype, ins, {o->output}, o->counts ? 0 : o->elements, 0,
+              o->tag, o->stream, counts);
   });
 }
 

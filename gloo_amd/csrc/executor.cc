@@ -265,6 +265,7 @@ struct PlanExecutor::HostShm {
 namespace {
 Plan planFor(int algo, int rank, int size, size_t count, int nin, int nout, size_t es, size_t maxSeg,
              const std::vector<int>& recvElems) {
+  if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, nin, recvElems);  // {counts}, or none
   if (isNewStyle(algo)) {
     NewStyleOptions o;
     o.ninputs = nin;
@@ -332,7 +333,7 @@ int32_t PlanExecutor::proposeSlices(const std::set<int>& recvPeers, int sliceCap
       std::vector<Access> remote;
       bool ok = true;
       for (int peer : recvPeers) {
-        const Plan theirs = planFor(planAlgo_, peer, P, count_, 0, 1, es_, maxSegmentBytes_, recvElems_);
+        const Plan theirs = planFor(planAlgo_, peer, P, count_, peerInputs(), 1, es_, maxSegmentBytes_, recvElems_);
         for (const Step& t : theirs.steps)
           if (t.kind == GLOO_HIP_STEP_SEND && t.peer == me) {
             auto it = decl.find({peer, t.slot});
@@ -430,7 +431,7 @@ void PlanExecutor::mapPeers(const std::vector<std::vector<char>>& arenas, const 
                        (void*)pr.ptr, ", ", pr.bytes, " B, slab ", pr.slabId, " of pid ", pr.pid, ", mapped at ", p,
                        ") ", kStaleImport, ": read ", seen, ", expected ", pr.nonce);
     }
-    const Plan theirs = planFor(planAlgo_, peer, P, count_, 0, 1, es_, maxSegmentBytes_, recvElems_);
+    const Plan theirs = planFor(planAlgo_, peer, P, count_, peerInputs(), 1, es_, maxSegmentBytes_, recvElems_);
     for (const Step& d : theirs.steps)
       if (d.kind == GLOO_HIP_STEP_DECL_RECV && d.peer == me) {
         GLOO_AMD_ENFORCE((d.dst_off + d.length) * es_ <= pr.bytes, "peer region outside its arena");
@@ -473,7 +474,7 @@ void PlanExecutor::configureDeviceLaunches() {
   for (const Step& s : plan_.steps) {
     if ((s.kind == GLOO_HIP_STEP_SEND || s.kind == GLOO_HIP_STEP_REDUCE || s.kind == GLOO_HIP_STEP_COPY ||
          s.kind == GLOO_HIP_STEP_LOCAL_REDUCE || s.kind == GLOO_HIP_STEP_LOCAL_BCAST ||
-         s.kind == GLOO_HIP_STEP_FOLD) &&
+         s.kind == GLOO_HIP_STEP_FOLD || s.kind == GLOO_HIP_STEP_LOCAL_GATHER) &&
         s.length * es_ > fuseBytes())
       unfused = true;
     maxMsg = std::max(maxMsg, (size_t)s.length * es_);
@@ -650,7 +651,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     }
     for (int r = 0; r < P && why.empty(); r++) {
       const Plan pr = r == me ? plan_
-                              : planFor(where[r].planAlgo, r, P, count_, 0, 1, es_, maxSegmentBytes_, recvElems_);
+                              : planFor(where[r].planAlgo, r, P, count_, peerInputs(), 1, es_, maxSegmentBytes_, recvElems_);
       if (exchangeHash(pr) != where[r].exchange)
         why = strcat_("rank ", r, "'s exchange steps differ from the plan every rank derives for it");
     }

@@ -166,6 +166,13 @@ bool sliceable(const Plan& plan, int nin, int nout, const std::vector<Access>& r
         }
         break;
       }
+      case GLOO_HIP_STEP_LOCAL_GATHER:
+        // input j whole into its own piece of the slot.  With more than one
+        // input the SEND of the slot then reads a range written in pieces,
+        // and the plan is refused: slice g of the block is not slice g of
+        // any one input.  One input writes exactly the range the SEND reads.
+        for (int j = 0; j < nin && ok; j++) ok = read({kIn + j, 0, L}) && write({0, t.dst_off + j * L, L});
+        break;
       case GLOO_HIP_STEP_LOCAL_BCAST:
         for (const auto& pc : cutRange(cuts, t.dst_off, L)) {
           ok = ok && read({0, pc.first, pc.second});
@@ -203,6 +210,9 @@ size_t slicedInterpSteps(const Plan& plan, int nin, int nout) {
       }
       case GLOO_HIP_STEP_LOCAL_BCAST:
         k += cutRange(cuts, t.dst_off, t.length).size() * (size_t)std::max(0, nout - 1);
+        break;
+      case GLOO_HIP_STEP_LOCAL_GATHER:  // one copy per input
+        k += (size_t)std::max(0, nin);
         break;
       default:
         k += 1;

@@ -121,6 +121,35 @@ size_t fanoutRun(const std::vector<Step>& steps, size_t i, std::vector<size_t>* 
   }
   return j;
 }
+// The sender's side of the allgather plan (plan.cc planAllgather) from step
+// i: the LOCAL_GATHER of `nin` inputs into the own slot, if any, then
+// (WAIT_NOTIFY | PREV_RUN (peer), SEND(the own block from output 0 to peer))+.
+// Returns the step after the run (i when step i does not start one) and the
+// SEND steps' indices; *gather: the run begins with the LOCAL_GATHER, whose
+// slot is exactly the block the SENDs read.
+size_t gatherRun(const std::vector<Step>& steps, size_t i, size_t nin, std::vector<size_t>* sends, bool* gather) {
+  size_t j = i;
+  sends->clear();
+  *gather = steps[i].kind == GLOO_HIP_STEP_LOCAL_GATHER;
+  if (*gather) {
+    if (nin == 0 || steps[i].length == 0) return i;
+    j++;
+  }
+  const size_t first = j;
+  while (j + 1 < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_NOTIFY && (steps[j].flags & GLOO_HIP_PREV_RUN) &&
+         steps[j + 1].kind == GLOO_HIP_STEP_SEND && steps[j + 1].peer == steps[j].peer && steps[j + 1].flags == 0 &&
+         steps[j + 1].length > 0 && steps[j + 1].dst_off == 0 && steps[j + 1].src_off == steps[first + 1].src_off &&
+         steps[j + 1].length == steps[first + 1].length) {
+    sends->push_back(j + 1);
+    j += 2;
+  }
+  if (*gather && !sends->empty()) {
+    const Step &g = steps[i], &s0 = steps[(*sends)[0]];
+    if (s0.src_off != g.dst_off || s0.length != g.length * nin) return i;
+  }
+  if (!*gather && sends->empty()) return i;
+  return j;
+}
 }  // namespace
 
 void markInterpBatches(InterpStep* v, size_t n, size_t es) {
@@ -184,8 +213,10 @@ void PlanExecutor::setStream(hipStream_t s) {
 }
 
 void PlanExecutor::setStreams(const std::vector<hipStream_t>& streams) {
-  GLOO_AMD_ENFORCE(streams.size() <= 1 || streams.size() == ptrs_.size(), "one stream per pointer: ",
-                   ptrs_.size(), " pointers, ", streams.size(), " streams");
+  // (an allgather's pointer list is {out, in_0 ...}: its inputs' streams are ordered like further pointers')
+  const size_t npointers = ptrs_.size() + (isAllgather(algo_) ? inputs_.size() : 0);
+  GLOO_AMD_ENFORCE(streams.size() <= 1 || streams.size() == npointers, "one stream per pointer: ",
+                   npointers, " pointers, ", streams.size(), " streams");
   hipStream_t next = streams.empty() ? nullptr : streams[0];
   for (hipStream_t t : streams) GLOO_AMD_ENFORCE(t != nullptr || streams.size() == 1, "null stream in the list");
   if (!next) {
@@ -665,6 +696,14 @@ void PlanExecutor::buildInterp() {
         for (const auto& pc : pieces(s))
           if (!bcast(pc.first, pc.second, nullptr)) return fail();
         break;
+      case GLOO_HIP_STEP_LOCAL_GATHER:
+        // one copy step per input (the SENDs of the slot stay as they are);
+        // inputs on another GPU of the process keep the enqueued plan, whose
+        // copies reach them directly
+        if (anyRemote_) return fail();
+        for (size_t j = 0; j < inputs_.size(); j++)
+          if (!copy(userPtr(0) + (s.dst_off + j * s.length) * es_, inPtr(j), s.length)) return fail();
+        break;
       case GLOO_HIP_STEP_FOLD_SRC:
         foldSrcs.push_back(sendSrc(s));
         break;
@@ -805,8 +844,81 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
   // first launch), then the local pointers; kMaxCopyEntries destinations a
   // launch, each launch with the ticket counter of its first peer's channel.
   const bool fanout = planAlgo_ == GLOO_HIP_ALGO_BROADCAST && deviceSignal_ && !anyRemote_;
+  // The allgather sender's LOCAL_GATHER and every SEND carry the same bytes:
+  // one wait for every peer's credit, then ONE pass that reads each input
+  // tile once and stores it to the own slot and into every peer's inbox
+  // (launchGatherFanout); in place, the fan-out of the own slot.  More than
+  // kMaxCopyEntries destinations go in batches, the first carrying the own
+  // slot, later ones reading the inputs again; each launch takes the ticket
+  // counter of its first peer's channel.  The receiver's credits go out in
+  // one launch.  Event profiling and inputs on other GPUs of the process
+  // keep the plan's own steps.
+  const bool gatherFanout = planAlgo_ == GLOO_HIP_ALGO_ALLGATHER && deviceSignal_ && !custom_ && !profiling_ &&
+                            !anyRemote_ && inputs_.size() <= (size_t)kMaxCopyEntries;
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
+    if (gatherFanout && (s.kind == GLOO_HIP_STEP_LOCAL_GATHER || s.kind == GLOO_HIP_STEP_WAIT_NOTIFY)) {
+      std::vector<size_t> sends;
+      bool gather = false;
+      const size_t next = gatherRun(steps, i, inputs_.size(), &sends, &gather);
+      if (next != i) {
+        std::vector<const uint64_t*> flags;
+        std::vector<Seq> targets;
+        for (size_t k : sends) {
+          const Step& w = steps[k - 1];
+          flags.push_back(waitFlag(w.peer, w.slot));
+          targets.push_back(seqOf(k - 1, r, graph));
+        }
+        if (!flags.empty())
+          GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                             ctx_->errorWordDevicePtr(me), stream_));
+        const size_t off = (gather ? s.dst_off : steps[sends[0]].src_off) * es_;
+        const size_t each = gather ? s.length * es_ : 0;  // bytes per input
+        const size_t block = gather ? each * inputs_.size() : steps[sends[0]].length * es_;
+        std::vector<FanoutDesc> dests;
+        std::vector<unsigned*> tickets;  // of each destination's channel (nullptr: the own slot)
+        if (gather) {
+          dests.push_back(FanoutDesc{userPtr(0) + off, nullptr, Seq{}});
+          tickets.push_back(nullptr);
+        }
+        for (size_t k : sends) {
+          const Step& t = steps[k];
+          dests.push_back(FanoutDesc{sendDst(t), sigFlag(t.peer, t.slot), seqOf(k, r, graph)});
+          tickets.push_back(ticket_ + (size_t)t.peer * GLOO_HIP_NUM_SLOTS + t.slot);
+        }
+        for (size_t b = 0; b < dests.size(); b += kMaxCopyEntries) {
+          const int nd = (int)std::min<size_t>(kMaxCopyEntries, dests.size() - b);
+          unsigned* ticket = nullptr;
+          for (int d = 0; d < nd && !ticket; d++) ticket = tickets[b + d];
+          if (gather) {
+            std::vector<const void*> srcs(inputs_.begin(), inputs_.end());
+            checkRc(launchGatherFanout(srcs.data(), (int)srcs.size(), each, dests.data() + b, nd, ticket, epoch,
+                                       gatherFanoutGrid(each, (int)srcs.size(), kFanoutBlocks), stream_),
+                    "gather_fanout_kernel");
+          } else {
+            checkRc(launchFanout(userPtr(0) + off, block, dests.data() + b, nd, ticket, epoch,
+                                 fanoutGrid(block, kFanoutBlocks), stream_),
+                    "fanout_kernel (allgather in place)");
+          }
+        }
+        i = next - 1;
+        continue;
+      }
+    }
+    // the allgather receiver's credits, one per sender: one launch
+    if (gatherFanout && s.kind == GLOO_HIP_STEP_NOTIFY && i + 1 < steps.size() &&
+        steps[i + 1].kind == GLOO_HIP_STEP_NOTIFY) {
+      std::vector<uint64_t*> flags;
+      std::vector<Seq> values;
+      size_t j = i;
+      for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_NOTIFY; j++) {
+        flags.push_back(sigFlag(steps[j].peer, steps[j].slot));
+        values.push_back(seqOf(j, r, graph));
+      }
+      GLOO_AMD_HIP_CHECK(launchSignalMulti(flags.data(), values.data(), (int)flags.size(), epoch, stream_));
+      i = j - 1;
+      continue;
+    }
     if (fanout && s.kind == GLOO_HIP_STEP_WAIT_NOTIFY) {
       std::vector<size_t> sends;
       bool withBcast = false;
@@ -1253,6 +1365,13 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
           GLOO_AMD_HIP_CHECK(hipMemcpyAsync(userPtr(j) + off, userPtr(0) + off, bytes, hipMemcpyDeviceToDevice, stream_));
         break;
       }
+      case GLOO_HIP_STEP_LOCAL_GATHER:
+        // the plan's own step (host signalling, profiling, inputs on another
+        // GPU of the process): one plain copy per input into its piece of the slot
+        for (size_t j = 0; j < inputs_.size() && s.length; j++)
+          GLOO_AMD_HIP_CHECK(hipMemcpyAsync(userPtr(0) + (s.dst_off + j * s.length) * es_, inputs_[j], s.length * es_,
+                                            hipMemcpyDeviceToDevice, stream_));
+        break;
       default:
         throw EnforceNotMet(strcat_("unknown plan step ", s.kind));
     }

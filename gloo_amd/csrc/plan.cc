@@ -1251,7 +1251,72 @@ Plan planBroadcast(int rank, int size, uint64_t count, int nptrs, int root) {
   return p;
 }
 
+// ---------------------------------------------------------------------------
+// GLOO_HIP_ALGO_ALLGATHER: AllgatherRing (gloo/allgather_ring.h), gloo::allgather
+// (gloo/allgather.cc) and gloo::allgatherv (gloo/allgatherv.cc).  The result
+// is the reference's: rank q's k inputs side by side at
+// out[k * (counts[0] + ... + counts[q-1])] (allgather_ring.h:19-24 and its
+// copy of the local buffers :65-68; allgatherv.cc:90-101 prefix offsets and
+// the priming of the output :103-112; in place = allgather.cc:47-54 with
+// in == nullptr, no LOCAL_GATHER).  The ROUTE departs: the reference passes
+// the blocks round a ring in P - 1 dependent hops (allgather_ring.h:70-91,
+// allgather.cc:69-96, allgatherv.cc:119-139); here every rank SENDs its own
+// block straight to every peer (a GPU has a link to each), the bytes that
+// arrive being the same.  The ring's "ready for an inbox write" notification
+// (allgather_ring.h:84-89) becomes one credit per (receiver, sender): the
+// receiver's NOTIFY after its COPY out of the inbox, awaited by the sender's
+// NEXT run (WAIT_NOTIFY | GLOO_HIP_PREV_RUN), so runs need no barrier.
+// Arena: laid out like the output, k * sum(counts) elements; peer q's inbox
+// is arena[offset(q), +k * counts[q]).  Empty blocks are skipped on both
+// sides, both knowing the counts (allgatherv.cc:106 skips its empty memcpy).
+// ---------------------------------------------------------------------------
+Plan planAllgather(int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
+  if (ninputs < 0) throw std::invalid_argument("allgather: " + std::to_string(ninputs) + " inputs");
+  if (!counts.empty() && (int)counts.size() != size)
+    throw std::invalid_argument("allgather: " + std::to_string(counts.size()) + " per-rank counts for " +
+                                std::to_string(size) + " ranks");
+  for (int q = 0; q < (int)counts.size(); q++)
+    if (counts[q] < 0)
+      throw std::invalid_argument("allgather: negative count " + std::to_string(counts[q]) + " for rank " +
+                                  std::to_string(q));
+  const uint64_t k = ninputs > 0 ? (uint64_t)ninputs : 1;  // in place: one block per rank
+  auto cnt = [&](int q) -> uint64_t { return counts.empty() ? count : (uint64_t)counts[q]; };
+  std::vector<uint64_t> off(size + 1, 0);
+  for (int q = 0; q < size; q++) off[q + 1] = off[q] + k * cnt(q);
+  Plan p;
+  if (off[size] == 0) return p;  // nothing to move
+  const uint64_t mine = k * cnt(rank);
+  std::vector<int> to, from;  // rank+1, rank+2, ... / rank-1, rank-2, ... with a block to send
+  for (int d = 1; d < size; d++) {
+    if (mine > 0) to.push_back((rank + d) % size);
+    const int q = (rank - d + size) % size;
+    if (cnt(q) > 0) from.push_back(q);
+  }
+  if (size > 1) p.arena = off[size];
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, q, GLOO_HIP_SLOT_DATA0, 0, off[q], 0, k * cnt(q)));
+  if (ninputs > 0 && mine > 0)                                           // allgather_ring.h:65-68
+    p.steps.push_back(mk(GLOO_HIP_STEP_LOCAL_GATHER, -1, 0, GLOO_HIP_FROM_INPUTS, off[rank], 0, cnt(rank)));
+  for (int q : to) {
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY, GLOO_HIP_PREV_RUN));
+    p.steps.push_back(mk(GLOO_HIP_STEP_SEND, q, GLOO_HIP_SLOT_DATA0, 0, 0, off[rank], mine));
+  }
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, q, GLOO_HIP_SLOT_DATA0));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, off[q], off[q], k * cnt(q)));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY));
+  for (int q : to) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_SEND, q, GLOO_HIP_SLOT_DATA0));
+  return p;
+}
+
 }  // namespace
+
+Plan makeAllgatherPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
+  if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
+  // every block goes to every rank in one hop already: there is nothing to derive
+  if (algo & GLOO_HIP_ALGO_MESH)
+    throw std::invalid_argument("allgather has no mesh form: algorithm " + std::to_string(algo) +
+                                " (GLOO_HIP_ALGO_ALLGATHER | GLOO_HIP_ALGO_MESH) is refused");
+  return planAllgather(rank, size, count, ninputs, counts);
+}
 
 Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewStyleOptions& o) {
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
@@ -1274,6 +1339,7 @@ Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewSty
 Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std::vector<int>& recvElems) {
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
   if (nptrs < 1) throw std::invalid_argument("need at least one pointer");
+  if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, 0, recvElems);  // in place
   if (algo & GLOO_HIP_ALGO_MESH) {
     const int base = algo & ~GLOO_HIP_ALGO_MESH;
     // an order of the reference's own route: a mesh plan has no first send
@@ -1333,7 +1399,11 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
     if ((algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_BROADCAST && recv_elems)
       re.assign(recv_elems, recv_elems + 2);  // {root, root pointer}
     gloo_amd::Plan p;
-    if (gloo_amd::isNewStyle(algo)) {
+    if (gloo_amd::isAllgather(algo)) {  // recv_elems: `size` per-rank counts, or NULL for `count` everywhere
+      if (noutputs != 1) throw std::invalid_argument("allgather has one output, not " + std::to_string(noutputs));
+      if (recv_elems && size > 0) re.assign(recv_elems, recv_elems + size);
+      p = gloo_amd::makeAllgatherPlan(algo, rank, size, count, ninputs, re);
+    } else if (gloo_amd::isNewStyle(algo)) {
       gloo_amd::NewStyleOptions o;
       o.ninputs = ninputs;
       o.noutputs = noutputs;

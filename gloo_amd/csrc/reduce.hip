@@ -1271,6 +1271,104 @@ __global__ __launch_bounds__(kCopyBlock) void fanout_kernel(const char* src, siz
 }
 
 // ---------------------------------------------------------------------------
+// Several sources, many destinations (signal.h launchGatherFanout): the
+// sender's side of GLOO_HIP_ALGO_ALLGATHER, its LOCAL_GATHER of the k inputs
+// into the rank's own slot of the output and the SENDs of that block into
+// every peer's inbox, which all carry the same bytes.  fanout_kernel
+// generalised to G.nsrc <= 8 sources of `bytes` bytes each: every
+// destination is a base address that receives the sources concatenated,
+// source s at dst + s * bytes, so every (source, destination) pair has its
+// own 16-byte misalignment.  Bytes only: no dtype, no op.  A capped grid
+// walks the (source, 16 KiB tile) space, `tiles` tile slots per source
+// (ceil(bytes / 16 KiB); a source whose head shortens its body leaves its
+// last slot empty): aligned `nt` loads from the source's first 16-B boundary,
+// each tile loaded once and stored to every destination through a descriptor
+// at the aligned-down address with the residue in soffset, write-through
+// into a peer's inbox (an entry with a flag), plain into the own slot (no
+// flag).  Each source's head and tail (< 16 bytes each) go byte-wise from
+// block 0, 32 lanes per source.  Completion exactly as fanout_kernel.  With
+// one source the stores are fanout_kernel's.
+// ---------------------------------------------------------------------------
+struct GatherList {
+  int nsrc;
+  const char* src[kMaxCopyEntries];
+};
+
+__global__ __launch_bounds__(kCopyBlock) void gather_fanout_kernel(GatherList G, size_t bytes, uint32_t tiles,
+                                                                   FanoutList F, const uint64_t* epoch) {
+  constexpr uint32_t kTileBytes = kCopyBlock * kCopyUnroll * 16;
+  bool edges = false;  // some source has head or tail bytes (block 0 stores them plain)
+  if (blockIdx.x == 0) {
+    const int s = threadIdx.x / 32;
+    const size_t t = threadIdx.x % 32;
+    for (int q = 0; q < G.nsrc; q++) {
+      const size_t m = (16 - (reinterpret_cast<uintptr_t>(G.src[q]) & 15)) & 15;
+      edges = edges || m != 0 || ((bytes - (m < bytes ? m : bytes)) & 15) != 0;
+    }
+    if (s < G.nsrc) {
+      const char* src = G.src[s];
+      const size_t mis = (16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15;
+      const size_t head = mis < bytes ? mis : bytes;
+      const size_t tail0 = head + (bytes - head) / 16 * 16;
+      // head < 16 and bytes - tail0 < 16: one lane per edge byte
+      if (t < head || (t >= 16 && tail0 + (t - 16) < bytes)) {
+        const size_t i = t < head ? t : tail0 + (t - 16);
+        const char c = src[i];
+        for (int r = 0; r < F.n; r++) F.dst[r][(size_t)s * bytes + i] = c;
+      }
+    }
+  }
+  const uint32_t lane_off = threadIdx.x * 16u;
+  const uint32_t work = (uint32_t)G.nsrc * tiles;  // 32 bits: the host refuses more (launchGatherFanout)
+  for (uint32_t w = blockIdx.x; w < work; w += gridDim.x) {
+    const uint32_t s = w / tiles;
+    const size_t base = (size_t)(w - s * tiles) * kTileBytes;
+    const char* src = G.src[s];
+    const size_t mis = (16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15;
+    const size_t head = mis < bytes ? mis : bytes;
+    const size_t body = (bytes - head) / 16 * 16;
+    if (base >= body) continue;
+    const uint32_t n = (uint32_t)((body - base) < kTileBytes ? (body - base) : kTileBytes);
+    const auto rs = make_rsrc(src + head + base, n);
+    u32x4 v[kCopyUnroll];
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; u++) v[u] = bload<kAuxNT>(rs, lane_off + u * kCopyBlock * 16);
+    for (int r = 0; r < F.n; r++) {
+      const Src dr = src_of(F.dst[r] + (size_t)s * bytes + head);
+      const auto rd = make_rsrc(dr.base + base, n + dr.mis);
+      if (F.flag[r]) {
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) bstore<kAuxWT>(rd, lane_off + u * kCopyBlock * 16, v[u], dr.mis);
+      } else {
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) bstore<0>(rd, lane_off + u * kCopyBlock * 16, v[u], dr.mis);
+      }
+    }
+  }
+  if (!F.ticket) return;  // the own slot only
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // as fanout_kernel: the bodies into the inboxes went out write-through
+    // and every wave has waited for them; only block 0, whose edge bytes are
+    // plain stores, releases before its ticket
+    if (blockIdx.x == 0 && edges) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const uint64_t ep = epoch ? *epoch : 0;
+    const unsigned t = __hip_atomic_fetch_add(F.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == gridDim.x - 1) {
+      __hip_atomic_store(F.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      for (int r = 0; r < F.n; r++)
+        if (F.flag[r])
+          __hip_atomic_store(F.flag[r], F.seq[r].base + ep * F.seq[r].perRun, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host-side dispatch.
 // ---------------------------------------------------------------------------
 int g_variant = 0;  // fp32 SUM kernel variant (measurement knob)
@@ -1648,6 +1746,44 @@ int launchFanout(const void* src, size_t bytes, const FanoutDesc* d, int n, unsi
   return check_launch("fanout_kernel");
 }
 
+unsigned gatherFanoutGrid(size_t bytes, int k, unsigned maxBlocks) {
+  const size_t tiles = (bytes + (size_t)kCopyBlock * kCopyUnroll * 16 - 1) / ((size_t)kCopyBlock * kCopyUnroll * 16);
+  const size_t work = tiles * (size_t)(k > 0 ? k : 1);
+  const size_t g = work < maxBlocks ? work : maxBlocks;
+  return (unsigned)(g == 0 ? 1 : g);
+}
+
+int launchGatherFanout(const void* const* srcs, int k, size_t bytes, const FanoutDesc* d, int n, unsigned* ticket,
+                       const uint64_t* epoch, unsigned grid, hipStream_t s) {
+  if (n < 1 || n > kMaxCopyEntries || grid == 0) return set_error(GLOO_HIP_EINVAL_ARG, "fan-out list size out of range");
+  if (k < 1 || k > kMaxCopyEntries || !srcs) return set_error(GLOO_HIP_EINVAL_ARG, "1..8 gather sources");
+  if (bytes == 0) return set_error(GLOO_HIP_EINVAL_ARG, "an empty gather has no launch");
+  const size_t tiles = (bytes + (size_t)kCopyBlock * kCopyUnroll * 16 - 1) / ((size_t)kCopyBlock * kCopyUnroll * 16);
+  if (tiles * (size_t)k > (size_t)1 << 31) return set_error(GLOO_HIP_EINVAL_ARG, "gather sources too large for one launch");
+  GatherList G;
+  memset(&G, 0, sizeof(G));
+  G.nsrc = k;
+  for (int i = 0; i < k; i++) {
+    if (!srcs[i]) return set_error(GLOO_HIP_EINVAL_PTR, "null gather source");
+    G.src[i] = static_cast<const char*>(srcs[i]);
+  }
+  FanoutList F;
+  memset(&F, 0, sizeof(F));
+  F.n = n;
+  bool flagged = false;
+  for (int j = 0; j < n; j++) {
+    if (!d[j].dst) return set_error(GLOO_HIP_EINVAL_PTR, "null fan-out destination");
+    F.dst[j] = static_cast<char*>(d[j].dst);
+    F.flag[j] = d[j].flag;
+    F.seq[j] = d[j].seq;
+    flagged = flagged || d[j].flag;
+  }
+  if (flagged && !ticket) return set_error(GLOO_HIP_EINVAL_ARG, "a signalled fan-out needs a ticket counter");
+  F.ticket = flagged ? ticket : nullptr;
+  gather_fanout_kernel<<<grid, kCopyBlock, 0, s>>>(G, bytes, (uint32_t)tiles, F, epoch);
+  return check_launch("gather_fanout_kernel");
+}
+
 struct CustomEntry {
   gloo_hip_custom_fn fn;
   void* user;
@@ -1907,6 +2043,18 @@ int gloo_hip_fanout_kernel(void* const* dsts, int n, const void* src, size_t byt
   return gloo_amd::launchFanout(src, bytes, d, n, nullptr, nullptr,
                                 gloo_amd::fanoutGrid(bytes, blocks ? blocks : gloo_amd::kFanoutBlocks),
                                 static_cast<hipStream_t>(stream));
+}
+
+int gloo_hip_gather_fanout_kernel(void* const* dsts, int n, const void* const* srcs, int k, size_t bytes,
+                                  unsigned blocks, gloo_hip_stream_t stream) {
+  if (n < 1 || n > gloo_amd::kMaxCopyEntries || !dsts) return set_error(GLOO_HIP_EINVAL_ARG, "1..8 destinations");
+  if (k < 1 || k > gloo_amd::kMaxCopyEntries || !srcs) return set_error(GLOO_HIP_EINVAL_ARG, "1..8 sources");
+  if (bytes == 0) return GLOO_HIP_OK;
+  gloo_amd::FanoutDesc d[gloo_amd::kMaxCopyEntries];
+  for (int j = 0; j < n; j++) d[j] = gloo_amd::FanoutDesc{dsts[j], nullptr, gloo_amd::Seq{}};
+  return gloo_amd::launchGatherFanout(srcs, k, bytes, d, n, nullptr, nullptr,
+                                      gloo_amd::gatherFanoutGrid(bytes, k, blocks ? blocks : gloo_amd::kFanoutBlocks),
+                                      static_cast<hipStream_t>(stream));
 }
 
 int gloo_hip_register_op(gloo_hip_custom_fn fn, void* user, int* op_out) {

@@ -70,6 +70,22 @@ __global__ __launch_bounds__(64) void wait_multi_kernel(WaitList w, const uint64
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
 }
 
+struct SignalList {
+  int n;
+  uint64_t* flag[kMaxWaitEntries];
+  Seq value[kMaxWaitEntries];
+};
+
+// as signal_kernel: one release by the wave, then a relaxed store per flag
+__global__ __launch_bounds__(64) void signal_multi_kernel(SignalList w, const uint64_t* epoch) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const int j = threadIdx.x;
+  if (j < w.n)
+    __hip_atomic_store(w.flag[j], seqValue(w.value[j].base, w.value[j].perRun, epoch), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Diagnosis of IPC mappings: the first word behind `p` read four ways.
 __global__ __launch_bounds__(64) void probe_kernel(const uint64_t* p, uint64_t* out) {
   if (threadIdx.x == 0) {
@@ -99,6 +115,22 @@ hipError_t launchWaitMulti(const uint64_t* const* flags, const Seq* targets, int
       w.target[j] = targets[i + j];
     }
     wait_multi_kernel<<<1, 64, 0, stream>>>(w, epoch, timeoutTicks, err);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launchSignalMulti(uint64_t* const* flags, const Seq* values, int n, const uint64_t* epoch,
+                             hipStream_t stream) {
+  for (int i = 0; i < n; i += kMaxWaitEntries) {
+    SignalList w;
+    w.n = n - i < kMaxWaitEntries ? n - i : kMaxWaitEntries;
+    for (int j = 0; j < w.n; j++) {
+      w.flag[j] = flags[i + j];
+      w.value[j] = values[i + j];
+    }
+    signal_multi_kernel<<<1, 64, 0, stream>>>(w, epoch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

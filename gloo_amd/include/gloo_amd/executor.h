@@ -181,6 +181,10 @@ class PlanExecutor {
   hipStream_t auxStream(size_t k);
   hipEvent_t forkEvent(size_t k);
   char* userPtr(int j) const { return static_cast<char*>(ptrs_[j]); }
+  // The input count a PEER's plan is derived with: the exchange steps of the
+  // allgather depend on it (block = k inputs; every rank passes the same k,
+  // and the exchange hash refuses ranks that do not); no other plan's do.
+  int peerInputs() const { return isAllgather(planAlgo_) ? (int)inputs_.size() : 0; }
 
   std::shared_ptr<Context> ctx_;
   int algo_, op_, dtype_;

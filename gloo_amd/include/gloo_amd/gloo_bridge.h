@@ -405,4 +405,41 @@ class HipBroadcastOneToAll : public Algorithm {
   gloo_hip_algorithm_t algo_ = nullptr;
 };
 
+// gloo::AllgatherRing (gloo/allgather_ring.h:25-32) on device pointers, the
+// reference constructor's argument order plus the streams of the GPU
+// algorithms: after run() outPtr holds every rank's inPtrs side by side, rank
+// q's at outPtr[q * inPtrs.size() * count] (:19-24).  GLOO_HIP_ALGO_ALLGATHER:
+// every rank sends its block straight to every peer instead of round the ring.
+// streams: none, or one per pointer of {outPtr, inPtrs...}.
+template <typename T, typename W = HipDeviceWorkspace<T>>
+class HipAllgatherRing : public Algorithm {
+ public:
+  HipAllgatherRing(const std::shared_ptr<Context>& context, const std::vector<const T*>& inPtrs, T* outPtr, int count,
+                   const std::vector<hipStream_t>& streams = std::vector<hipStream_t>())
+      : Algorithm(context) {
+    GLOO_ENFORCE(!inPtrs.empty(), "need at least one input");
+    GLOO_ENFORCE_GE(count, 0);
+    GLOO_ENFORCE(streams.empty() || streams.size() == inPtrs.size() + 1, "one stream per pointer, or none");
+    boot_.reset(new hip_bridge::BootstrapContext(context, hip_bridge::deviceOf(outPtr)));
+    std::vector<void*> p{outPtr};
+    for (const T* in : inPtrs) p.push_back(const_cast<T*>(in));
+    std::vector<gloo_hip_stream_t> s(streams.begin(), streams.end());
+    hip_bridge::check(
+        gloo_hip_algorithm_create_streams(boot_->handle(), GLOO_HIP_ALGO_ALLGATHER, 0 /* op: not used */,
+                                          hip_bridge::DType<T>::value, p.data(), (int)p.size(), (size_t)count, nullptr,
+                                          s.empty() ? nullptr : s.data(), (int)s.size(), W::kind, &algo_),
+        "gloo_hip_algorithm_create");
+  }
+
+  ~HipAllgatherRing() override {
+    if (algo_) (void)gloo_hip_algorithm_destroy(algo_);  // collective: a tear-down barrier
+  }
+
+  void run() override { hip_bridge::check(gloo_hip_algorithm_run(algo_), "run"); }
+
+ protected:
+  std::unique_ptr<hip_bridge::BootstrapContext> boot_;
+  gloo_hip_algorithm_t algo_ = nullptr;
+};
+
 }  // namespace gloo

@@ -13,6 +13,12 @@
 //        gloo/broadcast.cc:16-95)   ->  gloo::hip::broadcast(opts[, stream])
 //        (bytes only: no reduce function; one-to-all from the root instead of
 //        the reference's binomial tree, the same bytes on every rank)
+//   gloo::allgather(gloo::AllgatherOptions&)         (gloo/allgather.h,
+//        gloo/allgather.cc:19-97)   ->  gloo::hip::allgather(opts[, stream])
+//   gloo::allgatherv(gloo::AllgathervOptions&)       (gloo/allgatherv.h,
+//        gloo/allgatherv.cc:71-140) ->  gloo::hip::allgatherv(opts[, stream])
+//        (bytes only; every rank sends its block straight to every peer
+//        instead of round the reference's ring, the same bytes on every rank)
 //
 // The caller fills the SAME option object it would hand to gloo::allreduce /
 // gloo::reduce: setInput(s) / setOutput(s) with DEVICE pointers (the
@@ -48,6 +54,8 @@
 #include <utility>
 #include <vector>
 
+#include "gloo/allgather.h"
+#include "gloo/allgatherv.h"
 #include "gloo/allreduce.h"
 #include "gloo/broadcast.h"
 #include "gloo/math.h"
@@ -190,6 +198,37 @@ struct BroadcastAccess : ::gloo::BroadcastOptions {
   static uint32_t get_tag(const ::gloo::BroadcastOptions& o) { return o.*(&BroadcastAccess::tag); }
 };
 
+struct AllgatherAccess : ::gloo::AllgatherOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::AllgatherOptions& o) {
+    return o.*(&AllgatherAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::AllgatherOptions& o) {
+    return o.*(&AllgatherAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::AllgatherOptions& o) {
+    return o.*(&AllgatherAccess::out);
+  }
+  static size_t get_elementSize(const ::gloo::AllgatherOptions& o) { return o.*(&AllgatherAccess::elementSize); }
+  static uint32_t get_tag(const ::gloo::AllgatherOptions& o) { return o.*(&AllgatherAccess::tag); }
+};
+
+struct AllgathervAccess : ::gloo::AllgathervOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::AllgathervOptions& o) {
+    return o.*(&AllgathervAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::AllgathervOptions& o) {
+    return o.*(&AllgathervAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::AllgathervOptions& o) {
+    return o.*(&AllgathervAccess::out);
+  }
+  static const std::vector<size_t>& get_elements(const ::gloo::AllgathervOptions& o) {
+    return o.*(&AllgathervAccess::elements);
+  }
+  static size_t get_elementSize(const ::gloo::AllgathervOptions& o) { return o.*(&AllgathervAccess::elementSize); }
+  static uint32_t get_tag(const ::gloo::AllgathervOptions& o) { return o.*(&AllgathervAccess::tag); }
+};
+
 }  // namespace detail
 
 // A CUSTOM reduce function for the new-style calls: `host` is what the
@@ -298,6 +337,65 @@ inline void broadcast(::gloo::BroadcastOptions& opts, hipStream_t stream = nullp
   b.tag = A::get_tag(opts);
   b.stream = stream;
   ::gloo::hip_bridge::check(gloo_hip_broadcast(ctx, &b), "gloo::hip::broadcast");
+}
+
+// gloo::allgather(opts) (gloo/allgather.cc:19-97) on device buffers: every
+// rank's output receives rank 0's input, rank 1's input, ... back to back; no
+// input is the in-place form (:47-54).  The options carry an element size and
+// no type, and an allgather moves bytes, so the call goes down in uint8.
+inline void allgather(::gloo::AllgatherOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::AllgatherAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");
+  GLOO_ENFORCE(A::get_elementSize(opts) > 0);  // gloo/allgather.cc:26
+  const size_t outBytes = A::get_out(opts)->size;
+  if (A::get_in(opts)) {
+    GLOO_ENFORCE_EQ(outBytes, A::get_in(opts)->size * ctxp->size);  // gloo/allgather.cc:39
+  } else {
+    GLOO_ENFORCE_EQ(outBytes % ctxp->size, 0);  // gloo/allgather.cc:41
+  }
+  if (outBytes == 0) return;
+  void* out = A::get_out(opts)->ptr;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, out);
+  gloo_hip_allgather_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.input = A::get_in(opts) ? A::get_in(opts)->ptr : nullptr;
+  g.output = out;
+  g.elements = outBytes / ctxp->size;
+  g.counts = nullptr;
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_allgather(ctx, &g), "gloo::hip::allgather");
+}
+
+// gloo::allgatherv(opts) (gloo/allgatherv.cc:71-140): rank q contributes
+// elements[q] elements, the output at their prefix offsets (:90-101).
+inline void allgatherv(::gloo::AllgathervOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::AllgathervAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");
+  const size_t es = A::get_elementSize(opts);
+  GLOO_ENFORCE(es > 0);  // gloo/allgatherv.cc:78
+  std::vector<size_t> bytes;
+  size_t total = 0;
+  for (size_t e : A::get_elements(opts)) {
+    bytes.push_back(e * es);
+    total += e * es;
+  }
+  GLOO_ENFORCE_EQ(bytes.size(), (size_t)ctxp->size);
+  if (A::get_in(opts)) GLOO_ENFORCE_EQ(bytes[ctxp->rank], A::get_in(opts)->size);  // gloo/allgatherv.cc:105
+  if (total == 0) return;
+  void* out = A::get_out(opts)->ptr;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, out);
+  gloo_hip_allgather_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.input = A::get_in(opts) ? A::get_in(opts)->ptr : nullptr;
+  g.output = out;
+  g.elements = 0;
+  g.counts = bytes.data();
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_allgather(ctx, &g), "gloo::hip::allgatherv");
 }
 
 // Collective: tears down the library context (and its cached schedules)

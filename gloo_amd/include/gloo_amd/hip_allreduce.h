@@ -426,4 +426,112 @@ inline void broadcast(const BroadcastOptions& o) {
   exec.run();
 }
 
+// AllgatherRing (gloo/allgather_ring.h:25-32) over device pointers: after
+// run() outPtr holds, for every rank q in order, that rank's inPtrs side by
+// side (outPtr[q * inPtrs.size() * count], :19-24).  GLOO_HIP_ALGO_ALLGATHER:
+// the blocks go straight from every rank to every peer instead of round the
+// reference's ring, the same bytes.  streams: none, one (the plan's), or one
+// per pointer of {outPtr, inPtrs...}.
+template <typename T, typename W = HipDeviceWorkspace<T>>
+class HipAllgatherRing : public Algorithm {
+ public:
+  HipAllgatherRing(const std::shared_ptr<Context>& context, const std::vector<const T*>& inPtrs, T* outPtr, int count,
+                   const std::vector<hipStream_t>& streams = {})
+      : Algorithm(context) {
+    GLOO_AMD_ENFORCE(!inPtrs.empty(), "allgather: no input");
+    GLOO_AMD_ENFORCE(count >= 0, "allgather: negative count ", count);
+    GLOO_AMD_ENFORCE(streams.size() <= 1 || streams.size() == inPtrs.size() + 1,
+                     "one stream per pointer (the output first), one, or none");
+    std::vector<void*> ins;
+    for (const T* p : inPtrs) ins.push_back(const_cast<T*>(p));
+    exec_ = PlanExecutor::create(context, GLOO_HIP_ALGO_ALLGATHER, GLOO_HIP_SUM /* not used */, DType<T>::value,
+                                 std::vector<void*>{outPtr}, static_cast<size_t>(count), std::vector<int>{},
+                                 streams.empty() ? nullptr : streams[0], ins, 0, W::kind);
+    if (streams.size() > 1) exec_->setStreams(streams);
+  }
+  void run() override { exec_->run(); }
+
+ protected:
+  std::unique_ptr<PlanExecutor> exec_;
+};
+
+// gloo::AllgatherOptions (gloo/allgather.h) and gloo::AllgathervOptions
+// (gloo/allgatherv.h) over device pointers, in one class: setOutput with one
+// element count (the whole output, a multiple of the ranks) is the former,
+// with per-rank counts the latter.
+class AllgatherOptions {
+ public:
+  explicit AllgatherOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInput(T* ptr, size_t elements) {
+    input_ = ptr;
+    inputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, size_t elements) {
+    output_ = ptr;
+    outputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, std::vector<size_t> counts) {
+    output_ = ptr;
+    counts_ = std::move(counts);
+    dtype_ = DType<T>::value;
+  }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  void* input_ = nullptr;  // null: in place
+  void* output_ = nullptr;
+  size_t inputElements_ = 0, outputElements_ = 0;
+  std::vector<size_t> counts_;  // allgatherv: elements per rank
+  int dtype_ = GLOO_HIP_U8;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+using AllgathervOptions = AllgatherOptions;
+
+// gloo::allgatherv(opts) (gloo/allgatherv.cc:71-140): per-rank counts, the
+// output at their prefix offsets (:90-101).
+inline void allgatherv(const AllgatherOptions& o) {
+  const int P = o.context_->size;
+  GLOO_AMD_ENFORCE((int)o.counts_.size() == P, "allgatherv: ", o.counts_.size(), " counts for ", P, " ranks");  // .cc:66
+  std::vector<int> counts;
+  size_t total = 0;
+  for (size_t c : o.counts_) {
+    GLOO_AMD_ENFORCE(c <= (size_t)INT32_MAX, "allgatherv: count ", c, " is too large");
+    counts.push_back((int)c);
+    total += c;
+  }
+  GLOO_AMD_ENFORCE(!o.input_ || o.inputElements_ == o.counts_[o.context_->rank], "allgatherv: the input has ",
+                   o.inputElements_, " elements, this rank's count is ", o.counts_[o.context_->rank]);  // .cc:105
+  if (total == 0) return;
+  std::vector<void*> ins;
+  if (o.input_) ins.push_back(o.input_);
+  PlanExecutor exec(o.context_, GLOO_HIP_ALGO_ALLGATHER, GLOO_HIP_SUM /* not used */, o.dtype_, {o.output_}, 0, counts,
+                    o.stream_, ins);
+  exec.run();
+}
+
+// gloo::allgather(opts) (gloo/allgather.cc:19-97): the same count on every rank.
+inline void allgather(const AllgatherOptions& o) {
+  if (!o.counts_.empty()) return allgatherv(o);
+  const size_t P = (size_t)o.context_->size;
+  if (o.input_)
+    GLOO_AMD_ENFORCE(o.outputElements_ == o.inputElements_ * P, "allgather: output of ", o.outputElements_,
+                     " elements, ", P, " inputs of ", o.inputElements_);  // .cc:39
+  else
+    GLOO_AMD_ENFORCE(o.outputElements_ % P == 0, "allgather: output of ", o.outputElements_, " elements over ", P,
+                     " ranks");  // .cc:41
+  if (o.outputElements_ == 0) return;
+  std::vector<void*> ins;
+  if (o.input_) ins.push_back(o.input_);
+  PlanExecutor exec(o.context_, GLOO_HIP_ALGO_ALLGATHER, GLOO_HIP_SUM /* not used */, o.dtype_, {o.output_},
+                    o.outputElements_ / P, {}, o.stream_, ins);
+  exec.run();
+}
+
 }  // namespace gloo_amd

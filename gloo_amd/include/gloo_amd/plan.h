@@ -30,6 +30,12 @@ struct NewStyleOptions {
 // algo: GLOO_HIP_ALGO_ALLREDUCE_RING, GLOO_HIP_ALGO_ALLREDUCE_BCUBE or
 // GLOO_HIP_ALGO_REDUCE, optionally | GLOO_HIP_ALGO_MESH (mesh.h).
 Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewStyleOptions& o);
+// GLOO_HIP_ALGO_ALLGATHER (plan.cc planAllgather): `ninputs` inputs per rank
+// (0: in place, one block per rank already in its slot of the output) of
+// `count` elements each, or of counts[r] on rank r when `counts` has `size`
+// entries.  algo | GLOO_HIP_ALGO_MESH and a negative count are refused.
+Plan makeAllgatherPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts);
+inline bool isAllgather(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_ALLGATHER; }
 // Receives the text of a planner's refusal (an unknown algorithm, a mesh form
 // that does not exist, bad sizes) when gloo_hip_plan / gloo_hip_plan_ex return
 // GLOO_HIP_EINVAL_ARG.  The library installs its last-error text here

@@ -102,6 +102,23 @@ unsigned fanoutGrid(size_t bytes, unsigned maxBlocks);
 int launchFanout(const void* src, size_t bytes, const FanoutDesc* d, int n, unsigned* ticket, const uint64_t* epoch,
                  unsigned grid, hipStream_t stream);
 
+// k <= kMaxCopyEntries sources of `bytes` bytes each to up to kMaxCopyEntries
+// destinations in ONE pass (reduce.hip gather_fanout_kernel): every d[j].dst
+// receives the sources concatenated, source i at dst + i * bytes, each 16 KiB
+// source tile loaded once and stored to every destination at that pair's own
+// 16-byte misalignment.  Flags, stores, `ticket` and completion as
+// launchFanout, whose stores it makes for k = 1.  The sender's side of
+// GLOO_HIP_ALGO_ALLGATHER: the k inputs into the rank's own slot of the
+// output (no flag) and into every peer's inbox.  bytes > 0.
+unsigned gatherFanoutGrid(size_t bytes, int k, unsigned maxBlocks);
+int launchGatherFanout(const void* const* srcs, int k, size_t bytes, const FanoutDesc* d, int n, unsigned* ticket,
+                       const uint64_t* epoch, unsigned grid, hipStream_t stream);
+
+// Several signals in one launch: one system-scope release, then every
+// flags[j] := values[j] (a receiver's credits to all its senders).  Any n.
+hipError_t launchSignalMulti(uint64_t* const* flags, const Seq* values, int n, const uint64_t* epoch,
+                             hipStream_t stream);
+
 // Wait for several flags in one launch (one lane per flag), then ONE
 // system-scope acquire.  n <= kMaxWaitEntries.
 constexpr int kMaxWaitEntries = 16;

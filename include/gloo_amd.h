@@ -203,6 +203,17 @@ int gloo_hip_copy_kernel_multi(void* const* dsts, const void* const* srcs, const
 int gloo_hip_fanout_kernel(void* const* dsts, int n, const void* src, size_t bytes, unsigned blocks,
                            gloo_hip_stream_t stream);
 
+/* (new, tests and measurement) k <= 8 sources of `bytes` bytes each to up to
+ * 8 local destinations in ONE pass: every dsts[j] receives the sources
+ * concatenated (source i at dsts[j] + i * bytes), each 16 KiB source tile
+ * loaded once and stored to every destination at that (source, destination)
+ * pair's own 16-byte misalignment (the sender's pass of
+ * GLOO_HIP_ALGO_ALLGATHER without its flags; tools/allgather_bench.py).  With
+ * k = 1 it makes the stores of gloo_hip_fanout_kernel.  blocks: workgroups
+ * (0: one per tile, capped at 256). */
+int gloo_hip_gather_fanout_kernel(void* const* dsts, int n, const void* const* srcs, int k, size_t bytes,
+                                  unsigned blocks, gloo_hip_stream_t stream);
+
 /* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
  * is defined for (SUM..MIN on all twelve, BAND / BOR / BXOR on the six integer
  * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
@@ -306,6 +317,45 @@ typedef enum {
    * as one pass over the source (reduce.hip fanout_kernel) and the receiver's
    * COPY + LOCAL_BCAST as one pass over the inbox. */
   GLOO_HIP_ALGO_BROADCAST = 12,
+  /* AllgatherRing (gloo/allgather_ring.h), gloo::allgather and
+   * gloo::allgatherv (gloo/allgather.cc, gloo/allgatherv.cc): rank r
+   * contributes k >= 1 inputs of counts[r] elements each; block r is those
+   * inputs concatenated (k * counts[r] elements), and after a run every
+   * rank's ONE output holds block 0, block 1, ... block P-1 back to back
+   * (allgather_ring.h:19-24: outPtr[rank * ninputs * count] consecutively;
+   * allgatherv.cc:90-101: prefix offsets).  Not a reduction:
+   *   op     is NOT USED; any value is accepted, as for the broadcast.
+   *   dtype  gives the element size only; all twelve are valid.
+   *   ptrs   at gloo_hip_algorithm_create*: {out, in_0 ... in_{k-1}}, nptrs =
+   *          k + 1; nptrs = 1 is the in-place form (allgather.cc:47-54, in ==
+   *          nullptr): the rank's own block already sits in its slot of out.
+   *   count  elements per input; recv_elems NULL there.  In gloo_hip_plan_ex:
+   *          ninputs = k (0: in place, and then k is 1), noutputs = 1,
+   *          recv_elems = `size` per-rank counts or NULL for `count`
+   *          everywhere.  A negative count and | GLOO_HIP_ALGO_MESH are
+   *          refused with GLOO_HIP_EINVAL_ARG; the last-error text names the
+   *          value.
+   * Route: direct exchange.  The reference passes blocks round a ring in
+   * P - 1 dependent hops (allgather_ring.h:70-91, allgather.cc:69-96,
+   * allgatherv.cc:119-139); a GPU has a link to every peer, so every rank
+   * sends its block straight to every peer and the bytes that arrive are the
+   * same (the argument that made the broadcast one-to-all).
+   * Arena: laid out like the output, k * sum(counts) elements; the inbox for
+   * peer q is arena[offset(q), +k * counts[q]) on GLOO_HIP_SLOT_DATA0.
+   * Order, for P > 1 and a total > 0: DECL_RECVs; LOCAL_GATHER into the own
+   * slot (the reference's copy of the inputs, allgather_ring.h:65-68; absent
+   * in place); for each peer rank+1, rank+2, ...: WAIT_NOTIFY |
+   * GLOO_HIP_PREV_RUN on GLOO_HIP_SLOT_NOTIFY (the credit: that peer has
+   * copied LAST run's block out of its inbox), then SEND of the own block out
+   * of the output; for each peer rank-1, rank-2, ...: WAIT_RECV; one COPY
+   * arena -> output per peer; one NOTIFY (the credit) per peer; WAIT_SEND per
+   * peer sent to.  Empty blocks are skipped on both sides (both know the
+   * counts).  One rank: the LOCAL_GATHER alone; one rank in place, or a total
+   * of 0: no steps.  The credit orders run r + 1's send after run r's copy
+   * out of the inbox, so runs need no barrier.  The executor never promotes
+   * this plan; with device signalling the LOCAL_GATHER and every SEND are ONE
+   * pass that reads each input tile once (reduce.hip gather_fanout_kernel). */
+  GLOO_HIP_ALGO_ALLGATHER = 13,
 } gloo_hip_algo_t;
 
 /* algo | GLOO_HIP_ALGO_MESH: the algorithm's result with mesh data movement,
@@ -332,6 +382,8 @@ typedef enum {
   GLOO_HIP_STEP_FOLD = 11,       /* user[dst_off, +length) = fold of the pending FOLD_SRCs:
                                     acc = s0; acc = acc op s_k (or s_k op acc with
                                     GLOO_HIP_FOLD_REVERSE), k = 1.. in order             */
+  GLOO_HIP_STEP_LOCAL_GATHER = 12,/* for every input i: user[dst_off + i * length, +length)
+                                    = input_i[0, +length)  (GLOO_HIP_ALGO_ALLGATHER)      */
 } gloo_hip_step_kind_t;
 
 /* Message channels between a pair of ranks (the reference's slot roles). */
@@ -534,7 +586,8 @@ int gloo_hip_algorithm_stats(gloo_hip_algorithm_t algo, double* stats4);
  * abandoned, gloo_hip_last_error() says why. */
 int gloo_hip_algorithm_mode(gloo_hip_algorithm_t algo, int* mode4);
 /* The same for the schedule that ran the latest function-style call
- * (gloo_hip_allreduce / gloo_hip_reduce_to_root / gloo_hip_broadcast) on `ctx`. */
+ * (gloo_hip_allreduce / gloo_hip_reduce_to_root / gloo_hip_broadcast /
+ * gloo_hip_allgather) on `ctx`. */
 int gloo_hip_context_mode(gloo_hip_context_t ctx, int* mode4);
 
 /* ------------------------------------------------------------------------
@@ -610,6 +663,32 @@ typedef struct {
 } gloo_hip_broadcast_options_t;
 
 int gloo_hip_broadcast(gloo_hip_context_t ctx, const gloo_hip_broadcast_options_t* opts);
+
+/* ------------------------------------------------------------------------
+ * New-style function API: gloo::allgather(AllgatherOptions&)
+ * (gloo/allgather.h, gloo/allgather.cc) and gloo::allgatherv
+ * (gloo/allgatherv.h, gloo/allgatherv.cc) in one call: afterwards `output` on
+ * every rank holds rank 0's input, rank 1's input, ... back to back
+ * (`elements` each, or counts[r] with counts given: allgatherv's prefix
+ * offsets, allgatherv.cc:90-101).  input NULL is the in-place form
+ * (allgather.cc:47-54): the rank's own block already sits in its slot of the
+ * output.  The reference passes blocks round a ring; this runs the direct
+ * exchange of GLOO_HIP_ALGO_ALLGATHER (every rank sends its block straight to
+ * every peer), the same bytes.  Collective, cached per option set (dtype,
+ * counts, in place or not, tag) like gloo_hip_broadcast;
+ * gloo_hip_context_mode reports the schedule that ran.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int dtype;                /* gloo_hip_dtype_t: setInput<T>/setOutput<T>            */
+  void* input;              /* device pointer; NULL: in place                        */
+  void* output;             /* device pointer, the sum of the counts in elements     */
+  size_t elements;          /* per rank; ignored when counts is given                */
+  const size_t* counts;     /* NULL: `elements` on every rank; else `size` entries   */
+  uint32_t tag;             /* setTag                                                */
+  gloo_hip_stream_t stream; /* NULL: the output is complete on return                */
+} gloo_hip_allgather_options_t;
+
+int gloo_hip_allgather(gloo_hip_context_t ctx, const gloo_hip_allgather_options_t* opts);
 
 /* ------------------------------------------------------------------------
  * The xGMI transport: bound buffers of gloo::transport::Pair / Buffer
