@@ -1307,7 +1307,76 @@ Plan planAllgather(int rank, int size, uint64_t count, int ninputs, const std::v
   return p;
 }
 
+// ---------------------------------------------------------------------------
+// GLOO_HIP_ALGO_ALLTOALL: gloo::alltoall (gloo/alltoall.cc) and gloo::alltoallv
+// (gloo/alltoallv.cc).  One input and one output per rank, separate buffers.
+// The input is P blocks back to back, block q (in_counts[q] elements) for rank
+// q; the output is P blocks back to back, block q (out_counts[q] elements)
+// from rank q; offsets are the prefix sums (alltoallv.cc:19-31); the even form
+// has `count` everywhere (alltoall.cc:29-30).  The own block is a local copy
+// input -> output (alltoallv.cc:137-145), and in_counts[rank] ==
+// out_counts[rank] is enforced as there (:138).  The ROUTE is the reference's
+// own: every block goes straight to its peer.  A credit per (receiver,
+// sender), as the allgather's: the receiver's NOTIFY after its COPY out of the
+// inbox, awaited by the sender's NEXT run (WAIT_NOTIFY | GLOO_HIP_PREV_RUN).
+// Arena: laid out like the output; peer q's inbox is arena[outOff[q],
+// +out_counts[q]).  Empty blocks are skipped on both sides, both knowing the
+// counts (that in_counts_q[r] == out_counts_r[q] for every pair is for an
+// executor's construction to check before any byte moves; none runs this plan
+// yet).
+// ---------------------------------------------------------------------------
+Plan planAlltoall(int rank, int size, uint64_t count, const std::vector<int>& counts) {
+  if (!counts.empty() && (int)counts.size() != 2 * size)
+    throw std::invalid_argument("alltoall: " + std::to_string(counts.size()) + " counts for " + std::to_string(size) +
+                                " ranks (in_counts then out_counts: " + std::to_string(2 * size) + ")");
+  for (int q = 0; q < (int)counts.size(); q++)
+    if (counts[q] < 0)
+      throw std::invalid_argument("alltoall: negative " + std::string(q < size ? "in" : "out") + "_count " +
+                                  std::to_string(counts[q]) + " for rank " + std::to_string(q % size));
+  auto in = [&](int q) -> uint64_t { return counts.empty() ? count : (uint64_t)counts[q]; };
+  auto out = [&](int q) -> uint64_t { return counts.empty() ? count : (uint64_t)counts[size + q]; };
+  if (in(rank) != out(rank))  // alltoallv.cc:138
+    throw std::invalid_argument("alltoall: rank " + std::to_string(rank) + "'s own block has in_count " +
+                                std::to_string(in(rank)) + " but out_count " + std::to_string(out(rank)));
+  std::vector<uint64_t> inOff(size + 1, 0), outOff(size + 1, 0);
+  for (int q = 0; q < size; q++) {
+    inOff[q + 1] = inOff[q] + in(q);
+    outOff[q + 1] = outOff[q] + out(q);
+  }
+  Plan p;
+  std::vector<int> to, from;  // rank+1, rank+2, ... with a block to send / rank-1, rank-2, ... with one to receive
+  for (int d = 1; d < size; d++) {
+    const int t = (rank + d) % size, f = (rank - d + size) % size;
+    if (in(t) > 0) to.push_back(t);
+    if (out(f) > 0) from.push_back(f);
+  }
+  if (size > 1) p.arena = outOff[size];
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, q, GLOO_HIP_SLOT_DATA0, 0, outOff[q], 0, out(q)));
+  if (in(rank) > 0)  // alltoallv.cc:137-145
+    p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_FROM_INPUTS, outOff[rank], inOff[rank], in(rank)));
+  for (int q : to) {
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY, GLOO_HIP_PREV_RUN));
+    p.steps.push_back(mk(GLOO_HIP_STEP_SEND, q, GLOO_HIP_SLOT_DATA0, GLOO_HIP_FROM_INPUTS, 0, inOff[q], in(q)));
+  }
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, q, GLOO_HIP_SLOT_DATA0));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, outOff[q], outOff[q], out(q)));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY));
+  for (int q : to) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_SEND, q, GLOO_HIP_SLOT_DATA0));
+  return p;
+}
+
 }  // namespace
+
+Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
+  if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
+  // every block travels one hop already: there is nothing to derive
+  if (algo & GLOO_HIP_ALGO_MESH)
+    throw std::invalid_argument("alltoall has no mesh form: algorithm " + std::to_string(algo) +
+                                " (GLOO_HIP_ALGO_ALLTOALL | GLOO_HIP_ALGO_MESH) is refused");
+  if (ninputs != 1)
+    throw std::invalid_argument("alltoall has one input (no in-place form), not " + std::to_string(ninputs));
+  return planAlltoall(rank, size, count, counts);
+}
 
 Plan makeAllgatherPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
@@ -1340,6 +1409,8 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
   if (nptrs < 1) throw std::invalid_argument("need at least one pointer");
   if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, 0, recvElems);  // in place
+  // (GLOO_HIP_ALGO_ALLTOALL is a planner only so far: gloo_hip_plan / gloo_hip_plan_ex build it, no
+  // executor runs it, and it falls through to "unknown algorithm" here)
   if (algo & GLOO_HIP_ALGO_MESH) {
     const int base = algo & ~GLOO_HIP_ALGO_MESH;
     // an order of the reference's own route: a mesh plan has no first send
@@ -1382,6 +1453,15 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
 
 extern "C" int gloo_hip_plan(int algo, int rank, int size, size_t count, int nptrs, const int* recv_elems,
                              gloo_hip_step_t* steps, size_t capacity, size_t* nsteps, size_t* arena_elems) {
+  if (gloo_amd::isAlltoall(algo)) {  // the even form only: one input, one output, `count` per block
+    if (recv_elems) {
+      if (gloo_amd::planErrorSink)
+        gloo_amd::planErrorSink(GLOO_HIP_EINVAL_ARG, "alltoall: gloo_hip_plan takes the even form only (recv_elems "
+                                                     "must be NULL; per-block counts: gloo_hip_plan_ex)");
+      return GLOO_HIP_EINVAL_ARG;
+    }
+    return gloo_hip_plan_ex(algo, rank, size, count, 1, 1, 4, 0, nullptr, steps, capacity, nsteps, arena_elems);
+  }
   return gloo_hip_plan_ex(algo, rank, size, count, 0, nptrs, 4, 0, recv_elems, steps, capacity, nsteps,
                           arena_elems);
 }
@@ -1403,6 +1483,10 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
       if (noutputs != 1) throw std::invalid_argument("allgather has one output, not " + std::to_string(noutputs));
       if (recv_elems && size > 0) re.assign(recv_elems, recv_elems + size);
       p = gloo_amd::makeAllgatherPlan(algo, rank, size, count, ninputs, re);
+    } else if (gloo_amd::isAlltoall(algo)) {  // recv_elems: in_counts then out_counts (2 * size), or NULL: even
+      if (noutputs != 1) throw std::invalid_argument("alltoall has one output, not " + std::to_string(noutputs));
+      if (recv_elems && size > 0) re.assign(recv_elems, recv_elems + 2 * size);
+      p = gloo_amd::makeAlltoallPlan(algo, rank, size, count, ninputs, re);
     } else if (gloo_amd::isNewStyle(algo)) {
       gloo_amd::NewStyleOptions o;
       o.ninputs = ninputs;

@@ -36,6 +36,13 @@ Plan makeNewStylePlan(int algo, int rank, int size, uint64_t count, const NewSty
 // entries.  algo | GLOO_HIP_ALGO_MESH and a negative count are refused.
 Plan makeAllgatherPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts);
 inline bool isAllgather(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_ALLGATHER; }
+// GLOO_HIP_ALGO_ALLTOALL (plan.cc planAlltoall): one input and one output per
+// rank.  `counts` empty: the even form, `count` elements per block; else
+// 2 * size entries, this rank's in_counts[0..size) then out_counts[0..size).
+// algo | GLOO_HIP_ALGO_MESH, ninputs != 1, a negative count and in_counts[rank]
+// != out_counts[rank] are refused.
+Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts);
+inline bool isAlltoall(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_ALLTOALL; }
 // Receives the text of a planner's refusal (an unknown algorithm, a mesh form
 // that does not exist, bad sizes) when gloo_hip_plan / gloo_hip_plan_ex return
 // GLOO_HIP_EINVAL_ARG.  The library installs its last-error text here

@@ -356,6 +356,36 @@ typedef enum {
    * this plan; with device signalling the LOCAL_GATHER and every SEND are ONE
    * pass that reads each input tile once (reduce.hip gather_fanout_kernel). */
   GLOO_HIP_ALGO_ALLGATHER = 13,
+  /* gloo::alltoall and gloo::alltoallv (gloo/alltoall.cc, gloo/alltoallv.cc):
+   * A PLAN ONLY so far: gloo_hip_plan / gloo_hip_plan_ex build it; no executor
+   * runs it, and gloo_hip_algorithm_create* refuse the code as an unknown
+   * algorithm.  ONE input and ONE output per rank, separate buffers.  Rank r's
+   * input is P blocks back to back, block q (in_counts[q] elements) for rank
+   * q; its output is P blocks back to back, block q (out_counts[q] elements)
+   * from rank q; offsets are the prefix sums (alltoallv.cc:19-31):
+   *   out_r[outOff_r[q], +out_counts_r[q]) == in_q[inOff_q[r], +in_counts_q[r])
+   * gloo_hip_plan_ex(14, rank, size, count, ninputs = 1, noutputs = 1, ...,
+   * recv_elems): recv_elems NULL is the even form, `count` elements per block
+   * (alltoall.cc:29-30); otherwise it has 2 * size entries, in_counts[0..size)
+   * then out_counts[0..size), and count is ignored.  ninputs != 1, noutputs !=
+   * 1, a negative count, in_counts[rank] != out_counts[rank]
+   * (alltoallv.cc:138) and | GLOO_HIP_ALGO_MESH are refused with
+   * GLOO_HIP_EINVAL_ARG; the last-error text names the value.  gloo_hip_plan
+   * (the short form) takes the even form only.
+   * Route: the reference's own direct exchange, one hop per block.
+   * Arena: laid out like the output; the inbox for peer q is
+   * arena[outOff[q], +out_counts[q]) on GLOO_HIP_SLOT_DATA0; 0 at P = 1.
+   * Order, empty blocks skipped on both sides: DECL_RECVs; COPY |
+   * GLOO_HIP_FROM_INPUTS of the own block input -> output
+   * (alltoallv.cc:137-145); for each peer rank+1, rank+2, ...: WAIT_NOTIFY |
+   * GLOO_HIP_PREV_RUN on GLOO_HIP_SLOT_NOTIFY (the credit: that peer has
+   * copied LAST run's block out of its inbox), then SEND |
+   * GLOO_HIP_FROM_INPUTS of input block q; for each peer rank-1, rank-2, ...:
+   * WAIT_RECV; one COPY arena -> output per peer; one NOTIFY (the credit)
+   * per peer; WAIT_SEND per peer sent to.  One rank: the COPY alone.  A
+   * sender writes one-sidedly, so an executor of this plan has to check
+   * in_counts_q[r] == out_counts_r[q] for every pair before a byte moves. */
+  GLOO_HIP_ALGO_ALLTOALL = 14,
 } gloo_hip_algo_t;
 
 /* algo | GLOO_HIP_ALGO_MESH: the algorithm's result with mesh data movement,
@@ -403,7 +433,9 @@ typedef enum {
 /* LOCAL_REDUCE over [dst_off, +length) folds the separate INPUT buffers into
  * output 0 (new-style allreduce; one input = copy), instead of folding the
  * outputs into output 0.  On REDUCE: user[dst] = input0[dst] op arena[src]
- * (gloo::reduce's out = in op tmp); on SEND: the source is input 0. */
+ * (gloo::reduce's out = in op tmp); on SEND: the source is input 0; on COPY
+ * (GLOO_HIP_ALGO_ALLTOALL's own block, a plan no executor runs yet): the
+ * source is input 0 as well, user[dst_off, +length) = input0[src_off, +length). */
 #define GLOO_HIP_FROM_INPUTS 4
 /* FOLD: each new source is the LEFT operand (acc = s_k op acc). */
 #define GLOO_HIP_FOLD_REVERSE 8
