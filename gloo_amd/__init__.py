@@ -59,7 +59,7 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
             "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
-            "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel")
+            "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel")
 
 
 class GlooHipError(RuntimeError):
@@ -96,6 +96,9 @@ def _load():
     L.gloo_hip_fanout_kernel.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, sz, ctypes.c_uint, vp]
     L.gloo_hip_gather_fanout_kernel.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, sz,
                                                 ctypes.c_uint, vp]
+    L.gloo_hip_fold_kernel.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp), ctypes.c_int, sz, ctypes.c_int,
+                                       ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint64),
+                                       ctypes.c_int, vp, vp]
     return L
 
 
@@ -195,6 +198,22 @@ def gather_fanout_kernel(dsts, srcs, nbytes, blocks=0, stream=0):
     n, k = len(dsts), len(srcs)
     _check(lib.gloo_hip_gather_fanout_kernel((ctypes.c_void_p * n)(*dsts), n, (ctypes.c_void_p * k)(*srcs), k, nbytes,
                                              blocks, stream or None))
+
+
+def fold_kernel(op, dtype, dst, srcs, n, mode=0, fwd=(), fwd_flags=None, fwd_values=None, ticket=0, stream=0):
+    """gloo_hip_fold_kernel: the k-source fold as the executor launches it
+    (mode 0 left, 1 reverse, 2 tree), alone (no fwd: the FOLD step's kernel,
+    plain stores) or with up to 8 forward destinations (the fold + forward
+    kernel).  fwd[r] 0 / None with a flag is a credit; fwd_flags / fwd_values
+    are per forward (None: no flags, values 0); ticket: the zeroed device word
+    the flags need."""
+    k, nf = len(srcs), len(fwd)
+    vp = ctypes.c_void_p
+    flags = (vp * nf)(*[f or None for f in fwd_flags]) if fwd_flags is not None else None
+    values = (ctypes.c_uint64 * nf)(*fwd_values) if fwd_values is not None else None
+    _check(lib.gloo_hip_fold_kernel(_as_op(op), _as_dtype(dtype), dst, (vp * k)(*srcs), k, n, mode,
+                                    (vp * nf)(*[p or None for p in fwd]) if nf else None, flags, values, nf,
+                                    ticket or None, stream or None))
 
 
 def set_variant(v):

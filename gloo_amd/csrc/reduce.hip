@@ -2057,6 +2057,43 @@ int gloo_hip_gather_fanout_kernel(void* const* dsts, int n, const void* const* s
                                       static_cast<hipStream_t>(stream));
 }
 
+int gloo_hip_fold_kernel(int op, int dtype, void* dst, const void* const* srcs, int k, size_t n, int mode,
+                         void* const* fwd, uint64_t* const* fwd_flags, const uint64_t* fwd_values, int nfwd,
+                         unsigned* ticket, gloo_hip_stream_t stream) {
+  if (k < 1 || k > GLOO_HIP_MAX_SRCS) return set_error(GLOO_HIP_EINVAL_ARG, "source count out of range");
+  if (nfwd < 0 || nfwd > gloo_amd::kMaxCopyEntries) return set_error(GLOO_HIP_EINVAL_ARG, "forward count out of range");
+  if (mode < 0 || mode > 2) return set_error(GLOO_HIP_EINVAL_ARG, "unknown fold mode");
+  if (mode == 2 && (k & (k - 1))) return set_error(GLOO_HIP_EINVAL_ARG, "tree fold needs a power-of-two count");
+  const size_t es = gloo_hip_dtype_size(dtype);
+  if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+  if (!isBuiltinOp(op, dtype)) return set_error(GLOO_HIP_EINVAL_OP, "the fold kernels take a built-in op");
+  if (!dst) return set_error(GLOO_HIP_EINVAL_PTR, "null dst pointer");
+  if ((uintptr_t)dst % es) return set_error(GLOO_HIP_EINVAL_PTR, "dst not aligned to the element size");
+  if (!srcs) return set_error(GLOO_HIP_EINVAL_PTR, "null source list");
+  for (int j = 0; j < k; j++) {
+    if (!srcs[j]) return set_error(GLOO_HIP_EINVAL_PTR, "null source pointer");
+    if ((uintptr_t)srcs[j] % es) return set_error(GLOO_HIP_EINVAL_PTR, "source not aligned to the element size");
+  }
+  gloo_amd::FwdDesc d[gloo_amd::kMaxCopyEntries];
+  for (int r = 0; r < nfwd; r++) {
+    d[r] = gloo_amd::FwdDesc{fwd ? fwd[r] : nullptr, fwd_flags ? fwd_flags[r] : nullptr,
+                             gloo_amd::Seq{fwd_values ? fwd_values[r] : 0, 0}};
+    if (!d[r].dst && !d[r].flag) return set_error(GLOO_HIP_EINVAL_ARG, "forward entry with neither data nor flag");
+    if ((uintptr_t)d[r].dst % es)
+      return set_error(GLOO_HIP_EINVAL_PTR, "forward destination not aligned to the element size");
+    if (d[r].flag && !ticket) return set_error(GLOO_HIP_EINVAL_ARG, "forward flag without a ticket counter");
+  }
+  if (n == 0) return GLOO_HIP_OK;  // launchFoldSend has no such guard of its own
+  if (nfwd == 0) {
+    const bool prev = setReducePlainStores(true);  // the executor's FOLD step
+    const int rc = launchFold(op, dtype, dst, srcs, k, n, mode, static_cast<hipStream_t>(stream));
+    setReducePlainStores(prev);
+    return rc;
+  }
+  return launchFoldSend(op, dtype, dst, srcs, k, n, mode, d, nfwd, ticket, nullptr, static_cast<hipStream_t>(stream));
+}
+
 int gloo_hip_register_op(gloo_hip_custom_fn fn, void* user, int* op_out) {
   if (!fn || !op_out) return set_error(GLOO_HIP_EINVAL_ARG, "null argument");
   std::lock_guard<std::mutex> lk(customMutex());

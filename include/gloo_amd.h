@@ -214,6 +214,23 @@ int gloo_hip_fanout_kernel(void* const* dsts, int n, const void* src, size_t byt
 int gloo_hip_gather_fanout_kernel(void* const* dsts, int n, const void* const* srcs, int k, size_t bytes,
                                   unsigned blocks, gloo_hip_stream_t stream);
 
+/* (new, tests) The k-source fold kernels as a plan's executor launches them,
+ * without a peer: dst[i] = fold of srcs[0..k)[i], i < n, in `mode`'s order
+ * (0 left: acc = acc op s_j; 1 reverse: acc = s_j op acc; 2 balanced tree over
+ * the sources in order, k a power of two).  nfwd = 0: the FOLD step
+ * (reduce_multi_vec_kernel with plain stores).  nfwd in 1..8: the fold +
+ * forward (fold_send_kernel): every result element also goes to fwd[r] (any
+ * element-aligned address, its own 16-byte misalignment), and the launch's last
+ * workgroup stores fwd_values[r] to every non-null fwd_flags[r] and leaves
+ * *ticket (a zeroed device word, needed with any flag) at 0 again.  fwd[r] ==
+ * NULL with a flag is a credit: the flag alone.  fwd, fwd_flags and fwd_values
+ * may each be NULL (all entries NULL / 0).  dst may alias a source.  Built-in
+ * ops only.  Every argument is checked before any GPU call; n == 0 launches
+ * nothing.  Nothing in it waits on a flag (tests/test_fold_kernel_gpu.py). */
+int gloo_hip_fold_kernel(int op, int dtype, void* dst, const void* const* srcs, int k, size_t n, int mode,
+                         void* const* fwd, uint64_t* const* fwd_flags, const uint64_t* fwd_values, int nfwd,
+                         unsigned* ticket, gloo_hip_stream_t stream);
+
 /* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
  * is defined for (SUM..MIN on all twelve, BAND / BOR / BXOR on the six integer
  * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
