@@ -306,7 +306,14 @@ ALGORITHMS = {"ring_chunked": 0, "halving_doubling": 1, "ring": 2, "local": 3,
               "broadcast": 12,
               # AllgatherRing / gloo::allgather (GLOO_HIP_ALGO_ALLGATHER): ptrs = [out, in_0 ... in_{k-1}]
               # ([out]: in place), count elements per input; `op` is not used
-              "allgather": 13}
+              "allgather": 13,
+              # gloo::gather / gatherv (GLOO_HIP_ALGO_GATHER): ptrs = [in] ([in, out] on the root), recv_elems =
+              # [root] (count elements per rank) or [root, c_0 ... c_{P-1}] (gatherv); `op` is not used
+              "gather": 15,
+              # gloo::scatter (GLOO_HIP_ALGO_SCATTER): ptrs = [out] ([out, in_0 ... in_{P-1}] on the root),
+              # recv_elems = [root], count elements per rank; `op` is not used
+              "scatter": 16}
+COUNT_PER_RANK = (1 << (8 * ctypes.sizeof(ctypes.c_size_t))) - 1  # GLOO_HIP_COUNT_PER_RANK
 
 
 def _bind_collectives(L):
@@ -450,7 +457,7 @@ class Context:
 
     def last_mode(self):
         """How the latest function-style call (allreduce / reduce_to_root /
-        broadcast / allgather) on this context ran (see Algorithm.mode)."""
+        broadcast / allgather / gather / scatter) on this context ran (see Algorithm.mode)."""
         out = (ctypes.c_int * 4)()
         _check(lib.gloo_hip_context_mode(self._h, out))
         return _mode_dict(out)
@@ -493,6 +500,18 @@ class Algorithm:
             recv_elems = [int(root or 0), int(root_pointer or 0)]
         if (a & ~0x100) == ALGORITHMS["broadcast"]:  # the C side reads two entries
             recv_elems = (list(recv_elems or []) + [0, 0])[:2]
+        if (a & ~0x100) in (ALGORITHMS["gather"], ALGORITHMS["scatter"]):
+            # [root], or for a gather [root, c_0 ... c_{P-1}]: the C side reads the long form
+            # exactly when count is GLOO_HIP_COUNT_PER_RANK, so the length is checked here
+            name = "gather" if (a & ~0x100) == ALGORITHMS["gather"] else "scatter"
+            recv_elems = list(recv_elems or [])
+            long_form = name == "gather" and len(recv_elems) == 1 + ctx.size
+            if len(recv_elems) != 1 and not long_form:
+                raise GlooHipError(1, f"{name}: recv_elems has {len(recv_elems)} entries; [root]"
+                                   + (f" or [root, {ctx.size} per-rank counts]" if name == "gather" else "")
+                                   + " expected")
+            if long_form:
+                count = COUNT_PER_RANK
         arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
         rp = None
         if recv_elems is not None:
@@ -687,3 +706,73 @@ def allgather(ctx, output, elements, dtype, input=None, counts=None, tag=0, stre
     o.tag = tag
     o.stream = stream or None
     _check(lib.gloo_hip_allgather(ctx._h, ctypes.byref(o)))
+
+
+# ---- new-style function API: gloo::gather(opts) / gloo::gatherv(opts) / gloo::scatter(opts) --
+
+class GatherOptions(ctypes.Structure):
+    """gloo_hip_gather_options_t (mirrors gloo::GatherOptions, gloo/gather.h, and
+    gloo::GathervOptions, gloo/gatherv.h)."""
+    _fields_ = [("dtype", ctypes.c_int), ("root", ctypes.c_int), ("input", ctypes.c_void_p),
+                ("output", ctypes.c_void_p), ("elements", ctypes.c_size_t),
+                ("counts", ctypes.POINTER(ctypes.c_size_t)), ("tag", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
+class ScatterOptions(ctypes.Structure):
+    """gloo_hip_scatter_options_t (mirrors gloo::ScatterOptions, gloo/scatter.h)."""
+    _fields_ = [("dtype", ctypes.c_int), ("root", ctypes.c_int), ("output", ctypes.c_void_p),
+                ("inputs", ctypes.POINTER(ctypes.c_void_p)), ("elements", ctypes.c_size_t),
+                ("tag", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
+lib.gloo_hip_gather.argtypes = [ctypes.c_void_p, ctypes.POINTER(GatherOptions)]
+lib.gloo_hip_scatter.argtypes = [ctypes.c_void_p, ctypes.POINTER(ScatterOptions)]
+EXPORTED = EXPORTED + ("gloo_hip_gather", "gloo_hip_scatter")
+
+
+def gather(ctx, input, elements, dtype, root, output=None, counts=None, tag=0, stream=0):
+    """gloo::gather(opts) / gloo::gatherv(opts) on device pointers
+    (GLOO_HIP_ALGO_GATHER): afterwards the ROOT's output holds rank 0's input,
+    rank 1's input, ... back to back, `elements` each, or counts[r] with
+    counts (one entry per rank, the same list on every rank; elements is then
+    ignored).  A rank that is not the root has no output: it leaves output
+    None, and a pointer it passes is never written."""
+    if counts is not None and len(counts) != ctx.size:
+        raise GlooHipError(1, f"gather: {len(counts)} per-rank counts for {ctx.size} ranks")
+    o = GatherOptions()
+    o.dtype = _as_dtype(dtype)
+    o.root = int(root)
+    o.input = input or None
+    o.output = output or None
+    o.elements = int(elements)
+    arr = None
+    if counts is not None:
+        for q, c in enumerate(counts):
+            if int(c) < 0:
+                raise GlooHipError(1, f"gather: negative count {int(c)} for rank {q}")
+        arr = (ctypes.c_size_t * len(counts))(*[int(c) for c in counts])
+        o.counts = ctypes.cast(arr, ctypes.POINTER(ctypes.c_size_t))
+    o.tag = tag
+    o.stream = stream or None
+    _check(lib.gloo_hip_gather(ctx._h, ctypes.byref(o)))
+
+
+def scatter(ctx, output, elements, dtype, root, inputs=None, tag=0, stream=0):
+    """gloo::scatter(opts) on device pointers (GLOO_HIP_ALGO_SCATTER):
+    afterwards rank q's output holds the root's inputs[q], `elements`
+    elements.  inputs: on the root, one device pointer per rank (separate
+    buffers or slices of one allocation); None on every other rank."""
+    o = ScatterOptions()
+    o.dtype = _as_dtype(dtype)
+    o.root = int(root)
+    o.output = output or None
+    arr = None
+    if inputs is not None:
+        if len(inputs) != ctx.size:
+            raise GlooHipError(1, f"scatter: {len(inputs)} inputs for {ctx.size} ranks")
+        arr = (ctypes.c_void_p * len(inputs))(*[p or None for p in inputs])
+        o.inputs = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+    o.elements = int(elements)
+    o.tag = tag
+    o.stream = stream or None
+    _check(lib.gloo_hip_scatter(ctx._h, ctypes.byref(o)))

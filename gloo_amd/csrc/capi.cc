@@ -123,6 +123,45 @@ void allgatherArgs(int algo, void* const* ptrs, int nptrs, const int* recv_elems
   ins->assign(ptrs + 1, ptrs + nptrs);
   *op = GLOO_HIP_SUM;
 }
+
+// GLOO_HIP_ALGO_GATHER / GLOO_HIP_ALGO_SCATTER at the algorithm entry points
+// (include/gloo_amd.h).  Gather: ptrs = {in[, out]}, recv_elems = {root}, or
+// {root, c_0 ... c_{size-1}} with count == GLOO_HIP_COUNT_PER_RANK.  Scatter:
+// ptrs = {out[, in_0 ... in_{size-1}]}, recv_elems = {root}.  Every refusal is
+// made here, before any exchange with a peer: the planner's (the rank's own
+// plan is built once for them) and the pointer counts.  A gather rank
+// without an output hands the executor its input as "output 0": no step of
+// its plan reads or writes output 0, and the executor wants one pointer.
+// `op` is not used; the executor gets SUM, which every dtype has.
+void rootedArgs(int algo, int rank, int size, void* const* ptrs, int nptrs, size_t* count, const int* recv_elems,
+                std::vector<int>* re, std::vector<void*>* outs, std::vector<void*>* ins, int* op) {
+  const bool gather = gloo_amd::isGather(algo);
+  const char* name = gather ? "gather" : "scatter";
+  GLOO_AMD_ENFORCE(recv_elems, name, ": recv_elems is NULL ({root} expected)");
+  const bool perRank = gather && *count == GLOO_HIP_COUNT_PER_RANK;
+  re->assign(recv_elems, recv_elems + (perRank ? 1 + size : 1));
+  if (perRank) *count = 0;
+  try {
+    (void)(gather ? gloo_amd::makeGatherPlan(algo, rank, size, *count, *re)
+                  : gloo_amd::makeScatterPlan(algo, rank, size, *count, *re));
+  } catch (const std::invalid_argument& e) {
+    GLOO_AMD_ENFORCE(false, e.what());
+  }
+  const bool root = (*re)[0] == rank;
+  if (gather) {
+    GLOO_AMD_ENFORCE(!root || nptrs == 2, "gather: the root passes {input, output}, not ", nptrs, " pointers");
+    GLOO_AMD_ENFORCE(nptrs == 1 || nptrs == 2, "gather: {input} or {input, output}, not ", nptrs, " pointers");
+    ins->assign(1, ptrs[0]);
+    outs->assign(1, root ? ptrs[1] : ptrs[0]);
+  } else {
+    GLOO_AMD_ENFORCE(!root || nptrs == 1 + size, "scatter: the root passes {output, ", size, " inputs}, not ", nptrs,
+                     " pointers");
+    outs->assign(1, ptrs[0]);
+    ins->clear();
+    if (root) ins->assign(ptrs + 1, ptrs + nptrs);
+  }
+  *op = GLOO_HIP_SUM;
+}
 }  // namespace
 
 extern "C" {
@@ -163,7 +202,8 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
                                  gloo_hip_algorithm_t* out) {
   // refused on this rank before any exchange: every rank makes the same call
   // and fails alike, so nobody waits for a peer
-  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo))  // a broadcast / an allgather does not use its op
+  // a broadcast / an allgather / a gather / a scatter does not use its op
+  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo) && !gloo_amd::isRooted(algo))
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
@@ -181,6 +221,8 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
     }
     std::vector<void*> ins;
     if (gloo_amd::isAllgather(algo)) allgatherArgs(algo, ptrs, nptrs, recv_elems, &ps, &ins, &op);
+    if (gloo_amd::isRooted(algo))
+      rootedArgs(algo, ctx->ctx->rank, ctx->ctx->size, ptrs, nptrs, &count, recv_elems, &re, &ps, &ins, &op);
     auto a = std::make_unique<gloo_hip_algorithm>();
     a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
                                                        static_cast<hipStream_t>(stream), ins, 0, workspace);
@@ -192,13 +234,20 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
                                       int nptrs, size_t count, const int* recv_elems,
                                       const gloo_hip_stream_t* streams, int nstreams, int workspace,
                                       gloo_hip_algorithm_t* out) {
-  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo))
+  if (!isBroadcast(algo) && !gloo_amd::isAllgather(algo) && !gloo_amd::isRooted(algo))
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
     // gloo/cuda_allreduce_ring_chunked.cc:55-58
-    GLOO_AMD_ENFORCE(nstreams == 0 || (streams && nstreams == nptrs), "streams: ", nstreams, ", pointers: ", nptrs,
-                     " (one stream per pointer, or none)");
+    // a gather / a scatter: a rank's pointer count differs between the root and
+    // the others, and so would the stream lists; every rank passes one stream
+    // (the plan's) or none, whatever its pointer count
+    if (gloo_amd::isRooted(algo))
+      GLOO_AMD_ENFORCE(nstreams == 0 || (streams && nstreams == 1), "a gather / a scatter takes one stream or none, not ",
+                       nstreams);
+    else
+      GLOO_AMD_ENFORCE(nstreams == 0 || (streams && nstreams == nptrs), "streams: ", nstreams, ", pointers: ", nptrs,
+                       " (one stream per pointer, or none)");
     std::vector<int> re;
     if (algo == GLOO_HIP_ALGO_REDUCE_SCATTER) {
       GLOO_AMD_ENFORCE(recv_elems, "reduce-scatter needs recv_elems");
@@ -222,6 +271,8 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
                        " (one stream per pointer)");
     std::vector<void*> ins;  // an allgather: stream i stays with pointer i of {out, in_0 ...}
     if (gloo_amd::isAllgather(algo)) allgatherArgs(algo, ptrs, nptrs, recv_elems, &ps, &ins, &op);
+    if (gloo_amd::isRooted(algo))
+      rootedArgs(algo, ctx->ctx->rank, ctx->ctx->size, ptrs, nptrs, &count, recv_elems, &re, &ps, &ins, &op);
     auto a = std::make_unique<gloo_hip_algorithm>();
     a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, algo, op, dtype, ps, count, re,
                                              ss.empty() ? nullptr : ss[0], ins, 0, workspace);
@@ -392,6 +443,57 @@ int gloo_hip_allgather(gloo_hip_context_t ctx, const gloo_hip_allgather_options_
     if (o->input) ins.push_back(o->input);
     runCached(ctx, GLOO_HIP_ALGO_ALLGATHER, GLOO_HIP_SUM, o->dtype, ins, {o->output}, o->counts ? 0 : o->elements, 0,
               o->tag, o->stream, counts);
+  });
+}
+
+int gloo_hip_gather(gloo_hip_context_t ctx, const gloo_hip_gather_options_t* o) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && o, "null argument");
+    GLOO_AMD_ENFORCE(gloo_hip_dtype_size(o->dtype) > 0, "unknown dtype ", o->dtype);
+    const int P = ctx->ctx->size, me = ctx->ctx->rank;
+    GLOO_AMD_ENFORCE(o->root >= 0 && o->root < P, "gather: root rank ", o->root, " outside [0, ", P, ")");  // gather.cc:26
+    // {root}, or {root, c_0 ...}: the plan's recv_elems (ints)
+    std::vector<int> re{o->root};
+    size_t total = 0;
+    for (int q = 0; o->counts && q < P; q++) {
+      GLOO_AMD_ENFORCE(o->counts[q] <= (size_t)INT32_MAX, "gather: count ", o->counts[q], " of rank ", q,
+                       " is too large");
+      re.push_back((int)o->counts[q]);
+      total += o->counts[q];
+    }
+    if (!o->counts) total = o->elements * (size_t)P;
+    if (total == 0) return;
+    const size_t mine = o->counts ? o->counts[me] : o->elements;
+    GLOO_AMD_ENFORCE(o->input || mine == 0, "null input");  // gatherv.cc:79
+    GLOO_AMD_ENFORCE(me != o->root || o->output, "null output on the root");
+    // a rank without an output: the executor's one pointer is its input, which
+    // no step of its plan reads as output 0 or writes (construction is
+    // collective, so a rank with nothing to send still builds its executor)
+    void* in = o->input;
+    void* out = me == o->root ? o->output : in;
+    runCached(ctx, GLOO_HIP_ALGO_GATHER, GLOO_HIP_SUM, o->dtype, {in}, {out}, o->counts ? 0 : o->elements, 0, o->tag,
+              o->stream, re);
+  });
+}
+
+int gloo_hip_scatter(gloo_hip_context_t ctx, const gloo_hip_scatter_options_t* o) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && o, "null argument");
+    GLOO_AMD_ENFORCE(gloo_hip_dtype_size(o->dtype) > 0, "unknown dtype ", o->dtype);
+    const int P = ctx->ctx->size, me = ctx->ctx->rank;
+    GLOO_AMD_ENFORCE(o->root >= 0 && o->root < P, "scatter: root rank ", o->root, " outside [0, ", P, ")");  // scatter.cc:27
+    if (o->elements == 0) return;
+    GLOO_AMD_ENFORCE(o->output, "null output");  // scatter.cc:28
+    std::vector<void*> ins;
+    if (me == o->root) {
+      GLOO_AMD_ENFORCE(o->inputs, "scatter: the root has no inputs");  // scatter.cc:31
+      for (int q = 0; q < P; q++) {
+        GLOO_AMD_ENFORCE(o->inputs[q], "scatter: null input for rank ", q);
+        ins.push_back(o->inputs[q]);
+      }
+    }
+    runCached(ctx, GLOO_HIP_ALGO_SCATTER, GLOO_HIP_SUM, o->dtype, ins, {o->output}, o->elements, 0, o->tag, o->stream,
+              {o->root});
   });
 }
 

@@ -77,7 +77,7 @@ std::vector<size_t> userCuts(const Plan& plan) {
         add(t.dst_off, t.length);
         break;
       case GLOO_HIP_STEP_COPY:
-        if (!(t.flags & GLOO_HIP_SRC_ARENA)) add(t.src_off, t.length);
+        if (!(t.flags & (GLOO_HIP_SRC_ARENA | GLOO_HIP_FROM_INPUTS))) add(t.src_off, t.length);
         if (!(t.flags & GLOO_HIP_DST_ARENA)) add(t.dst_off, t.length);
         break;
       case GLOO_HIP_STEP_FOLD:
@@ -136,7 +136,7 @@ bool sliceable(const Plan& plan, int nin, int nout, const std::vector<Access>& r
   for (const Access& w : remoteWrites)
     if (!write(w)) return false;
   auto sendBuf = [](const Step& t) {
-    return t.flags & GLOO_HIP_SRC_ARENA ? kArena : t.flags & GLOO_HIP_FROM_INPUTS ? kIn : 0;
+    return t.flags & GLOO_HIP_SRC_ARENA ? kArena : t.flags & GLOO_HIP_FROM_INPUTS ? kIn + GLOO_HIP_INPUT_OF(t.flags) : 0;
   };
   for (const Step& t : plan.steps) {
     const size_t L = t.length;
@@ -151,7 +151,7 @@ bool sliceable(const Plan& plan, int nin, int nout, const std::vector<Access>& r
              write({0, t.dst_off, L});
         break;
       case GLOO_HIP_STEP_COPY:
-        ok = read({t.flags & GLOO_HIP_SRC_ARENA ? kArena : 0, t.src_off, L}) &&
+        ok = read({sendBuf(t), t.src_off, L}) &&  // (a rooted collective's own block: COPY | FROM_INPUTS)
              write({t.flags & GLOO_HIP_DST_ARENA ? kArena : 0, t.dst_off, L});
         break;
       case GLOO_HIP_STEP_FOLD:

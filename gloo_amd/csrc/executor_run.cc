@@ -528,7 +528,12 @@ void PlanExecutor::buildInterp() {
   };
   auto sendSrc = [&](const Step& t) -> const char* {
     if (t.flags & GLOO_HIP_SRC_ARENA) return arenaAt(t.src_off, t.length);
-    return (t.flags & GLOO_HIP_FROM_INPUTS ? inPtr(0) : userPtr(0)) + t.src_off * es_;
+    return (t.flags & GLOO_HIP_FROM_INPUTS ? inPtr(GLOO_HIP_INPUT_OF(t.flags)) : userPtr(0)) + t.src_off * es_;
+  };
+  // a COPY's source: the arena, the input its flags name (a rooted collective's own block) or output 0
+  auto copySrc = [&](const Step& t) -> const char* {
+    if (t.flags & GLOO_HIP_FROM_INPUTS) return inPtr(GLOO_HIP_INPUT_OF(t.flags)) + t.src_off * es_;
+    return userOrArena(t.flags & GLOO_HIP_SRC_ARENA, t.src_off, t.length);
   };
   std::vector<InterpStep> v;
   auto push = [&](int kind) -> InterpStep& {
@@ -597,6 +602,10 @@ void PlanExecutor::buildInterp() {
                          !custom_ && !anyRemote_;
   std::vector<const char*> foldSrcs;
   const std::vector<Step>& steps = plan_.steps;
+  // a gather's or a scatter's inputs on another GPU of the process keep the
+  // enqueued plan, whose copies reach them directly (they are not staged:
+  // their sizes are per block, not count_)
+  if (isRooted(planAlgo_) && anyRemote_) return fail();
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     const size_t bytes = s.length * es_;
@@ -665,9 +674,7 @@ void PlanExecutor::buildInterp() {
         break;
       }
       case GLOO_HIP_STEP_COPY:
-        if (!copy(userOrArena(s.flags & GLOO_HIP_DST_ARENA, s.dst_off, s.length),
-                  userOrArena(s.flags & GLOO_HIP_SRC_ARENA, s.src_off, s.length), s.length))
-          return fail();
+        if (!copy(userOrArena(s.flags & GLOO_HIP_DST_ARENA, s.dst_off, s.length), copySrc(s), s.length)) return fail();
         break;
       case GLOO_HIP_STEP_LOCAL_REDUCE:  // as enqueue(): chained folds of <= GLOO_HIP_MAX_SRCS sources
         // sliced: one piece per range the other steps use (userCuts)
@@ -777,8 +784,15 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
   // a SEND's source: the arena, input 0 (gloo::reduce's first segments) or output 0
   auto sendSrc = [&](const Step& t) -> const char* {
     if (t.flags & GLOO_HIP_SRC_ARENA) return arenaAt(t.src_off, t.length);
-    return (t.flags & GLOO_HIP_FROM_INPUTS ? static_cast<const char*>(inputs_.at(0)) : userPtr(0)) +
+    return (t.flags & GLOO_HIP_FROM_INPUTS ? static_cast<const char*>(inputs_.at(GLOO_HIP_INPUT_OF(t.flags)))
+                                           : userPtr(0)) +
            t.src_off * es_;
+  };
+  // a COPY's source: the arena, the input its flags name (a rooted collective's own block) or output 0
+  auto copySrc = [&](const Step& t) -> const char* {
+    if (t.flags & GLOO_HIP_FROM_INPUTS)
+      return static_cast<const char*>(inputs_.at(GLOO_HIP_INPUT_OF(t.flags))) + t.src_off * es_;
+    return userOrArena(t.flags & GLOO_HIP_SRC_ARENA, t.src_off, t.length);
   };
   const std::vector<Step>& steps = plan_.steps;
   auto sendDst = [&](const Step& t) {
@@ -855,8 +869,118 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
   // keep the plan's own steps.
   const bool gatherFanout = planAlgo_ == GLOO_HIP_ALGO_ALLGATHER && deviceSignal_ && !custom_ && !profiling_ &&
                             !anyRemote_ && inputs_.size() <= (size_t)kMaxCopyEntries;
+  // The rooted collectives (plan.cc planScatter / planGather) with device
+  // signalling.  A scatter root's sends read P - 1 different inputs, a gather
+  // root's copy-outs P - 1 different inbox regions: independent (src -> dst)
+  // ranges, which the multi-copy launch already moves at once, each with its
+  // own flag.  Scatter root: ONE wait for every clear-to-send, then the sends
+  // (flagged, one channel each) and the own block (no flag, plain stores) as
+  // entries of launchCopySignalMulti, kMaxCopyEntries a launch.  Gather root:
+  // ONE wait for every arrival, the own block and the copy-outs as entries of
+  // the same launch (plain stores), the credits in one launchSignalMulti.  A
+  // gather sender and a scatter receiver are a wait and a lone SEND / COPY:
+  // the ordinary routes below.  Event profiling and inputs on other GPUs of
+  // the process keep the plan's own steps.
+  const bool rooted = isRooted(planAlgo_) && deviceSignal_ && !profiling_ && !anyRemote_;
+  // The own block joins that launch only when it shares no byte with
+  // anything else the launch touches (its own two ranges, the sends' sources,
+  // the copy-outs' destinations); an in-place or overlapping buffer keeps the
+  // plan's COPY step in the plan's order (include/gloo_amd.h, "Buffers").
+  auto disjoint = [](const char* a, size_t na, const char* b, size_t nb) { return a + na <= b || b + nb <= a; };
+  auto localCopies = [&](const std::vector<CopyDesc>& d, const char* what) {
+    for (size_t b = 0; b < d.size(); b += kMaxCopyEntries)
+      checkRc(launchCopySignalMulti(d.data() + b, (int)std::min<size_t>(kMaxCopyEntries, d.size() - b), epoch, stream_,
+                                    kCopyStorePlain),
+              what);
+  };
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
+    if (rooted && isScatter(planAlgo_) && s.kind == GLOO_HIP_STEP_WAIT_NOTIFY) {
+      size_t j = i;
+      std::vector<const uint64_t*> flags;
+      std::vector<Seq> targets;
+      std::vector<CopyDesc> d;
+      while (j + 1 < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_NOTIFY && steps[j + 1].kind == GLOO_HIP_STEP_SEND &&
+             steps[j + 1].peer == steps[j].peer && (steps[j + 1].flags & GLOO_HIP_FROM_INPUTS) && steps[j + 1].length > 0) {
+        const Step& t = steps[j + 1];
+        const size_t bytes = t.length * es_;
+        flags.push_back(waitFlag(steps[j].peer, steps[j].slot));
+        targets.push_back(seqOf(j, r, graph));
+        d.push_back(CopyDesc{sendDst(t), sendSrc(t), bytes, sigFlag(t.peer, t.slot), seqOf(j + 1, r, graph),
+                             ticket_ + (size_t)t.peer * GLOO_HIP_NUM_SLOTS + t.slot,
+                             copySignalGrid(bytes, copyBlocksFor(t.peer))});
+        j += 2;
+      }
+      if (!d.empty()) {
+        if (j < steps.size() && steps[j].kind == GLOO_HIP_STEP_COPY && (steps[j].flags & GLOO_HIP_FROM_INPUTS) &&
+            steps[j].length > 0) {
+          const Step& c = steps[j];
+          char* dst = userPtr(0) + c.dst_off * es_;
+          const char* src = copySrc(c);
+          const size_t bytes = c.length * es_;
+          bool joins = disjoint(dst, bytes, src, bytes);
+          for (const CopyDesc& e : d) joins = joins && disjoint(dst, bytes, static_cast<const char*>(e.src), e.bytes);
+          if (joins) {
+            d.push_back(CopyDesc{dst, src, bytes, nullptr, Seq{}, nullptr, copySignalGrid(bytes, kCopyOutBlocks)});
+            j++;
+          }
+        }
+        GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                           ctx_->errorWordDevicePtr(me), stream_));
+        localCopies(d, "copy_signal_kernel (scatter root)");
+        i = j - 1;
+        continue;
+      }
+    }
+    if (rooted && isGather(planAlgo_) &&
+        (s.kind == GLOO_HIP_STEP_WAIT_RECV ||
+         (s.kind == GLOO_HIP_STEP_COPY && (s.flags & GLOO_HIP_FROM_INPUTS) && s.length > 0 && i + 1 < steps.size() &&
+          steps[i + 1].kind == GLOO_HIP_STEP_WAIT_RECV))) {
+      std::vector<CopyDesc> d;
+      size_t j = i;
+      bool joins = true;
+      if (s.kind == GLOO_HIP_STEP_COPY) {
+        char* dst = userPtr(0) + s.dst_off * es_;
+        const char* src = copySrc(s);
+        const size_t bytes = s.length * es_;
+        joins = disjoint(dst, bytes, src, bytes);
+        for (size_t k = i + 1; k < steps.size() && (steps[k].kind == GLOO_HIP_STEP_WAIT_RECV ||
+                                                    (steps[k].kind == GLOO_HIP_STEP_COPY && steps[k].flags == GLOO_HIP_SRC_ARENA));
+             k++)
+          if (steps[k].kind == GLOO_HIP_STEP_COPY)
+            joins = joins && disjoint(src, bytes, userPtr(0) + steps[k].dst_off * es_, steps[k].length * es_);
+        if (joins) d.push_back(CopyDesc{dst, src, bytes, nullptr, Seq{}, nullptr, copySignalGrid(bytes, kCopyOutBlocks)});
+        j++;
+      }
+      if (joins) {  // (else: this COPY stays a step, and the pass starts at the WAIT_RECV after it)
+        std::vector<const uint64_t*> flags;
+        std::vector<Seq> targets;
+        for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_RECV; j++) {
+          flags.push_back(waitFlag(steps[j].peer, steps[j].slot));
+          targets.push_back(seqOf(j, r, graph));
+        }
+        for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_COPY && steps[j].flags == GLOO_HIP_SRC_ARENA; j++) {
+          const Step& t = steps[j];
+          const size_t bytes = t.length * es_;
+          if (bytes)
+            d.push_back(CopyDesc{userPtr(0) + t.dst_off * es_, arenaAt(t.src_off, t.length), bytes, nullptr, Seq{}, nullptr,
+                                 copySignalGrid(bytes, kCopyOutBlocks)});
+        }
+        std::vector<uint64_t*> credits;
+        std::vector<Seq> values;
+        for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_NOTIFY; j++) {
+          credits.push_back(sigFlag(steps[j].peer, steps[j].slot));
+          values.push_back(seqOf(j, r, graph));
+        }
+        GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                           ctx_->errorWordDevicePtr(me), stream_));
+        localCopies(d, "copy kernel (gather root)");
+        if (!credits.empty())
+          GLOO_AMD_HIP_CHECK(launchSignalMulti(credits.data(), values.data(), (int)credits.size(), epoch, stream_));
+        i = j - 1;
+        continue;
+      }
+    }
     if (gatherFanout && (s.kind == GLOO_HIP_STEP_LOCAL_GATHER || s.kind == GLOO_HIP_STEP_WAIT_NOTIFY)) {
       std::vector<size_t> sends;
       bool gather = false;
@@ -1077,8 +1201,7 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
       std::vector<size_t> lens;
       for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_COPY && ops.size() < (size_t)kMaxCopyEntries; j++) {
         const Step& t = steps[j];
-        ops.push_back({userOrArena(t.flags & GLOO_HIP_DST_ARENA, t.dst_off, t.length),
-                       userOrArena(t.flags & GLOO_HIP_SRC_ARENA, t.src_off, t.length)});
+        ops.push_back({userOrArena(t.flags & GLOO_HIP_DST_ARENA, t.dst_off, t.length), copySrc(t)});
         lens.push_back(t.length * es_);
       }
       bool disjoint = true;
@@ -1133,7 +1256,7 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
           src = arenaAt(t->src_off, t->length);
         } else if (t->kind == GLOO_HIP_STEP_COPY) {
           dst = userOrArena(t->flags & GLOO_HIP_DST_ARENA, t->dst_off, t->length);
-          src = userOrArena(t->flags & GLOO_HIP_SRC_ARENA, t->src_off, t->length);
+          src = copySrc(*t);
         } else {
           dst = peerAt(t->peer, remoteRegion_[{t->peer, t->slot}] + t->dst_off, t->length);
           src = sendSrc(*t);
@@ -1229,7 +1352,7 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
       }
       case GLOO_HIP_STEP_COPY: {
         char* dst = userOrArena(s.flags & GLOO_HIP_DST_ARENA, s.dst_off, s.length);
-        const char* src = userOrArena(s.flags & GLOO_HIP_SRC_ARENA, s.src_off, s.length);
+        const char* src = copySrc(s);
         const size_t bytes = s.length * es_;
         if (deviceSignal_ && bytes > 0 && (dst + bytes <= src || src + bytes <= dst)) {
           const CopyDesc d{dst, src, bytes, nullptr, Seq{}, nullptr, copySignalGrid(bytes, kCopyOutBlocks)};

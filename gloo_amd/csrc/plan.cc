@@ -1365,7 +1365,116 @@ Plan planAlltoall(int rank, int size, uint64_t count, const std::vector<int>& co
   return p;
 }
 
+// ---------------------------------------------------------------------------
+// GLOO_HIP_ALGO_GATHER: gloo::gather (gloo/gather.cc) and gloo::gatherv
+// (gloo/gatherv.cc).  One input per rank; the root's one output ends as block
+// 0 ... block P-1 back to back (gather.cc:40-47; gatherv.cc:82-96, prefix
+// offsets).  The route is the reference's: every block straight to the root
+// (gatherv.cc:87, :104).  The root's arena is laid out like its output; peer
+// q's inbox is arena[off[q], +c_q).  The reference receives into the output
+// itself; here a message lands in the inbox and is copied out, and the root's
+// NOTIFY after that COPY is the credit the sender's NEXT run waits for
+// (WAIT_NOTIFY | GLOO_HIP_PREV_RUN, the allgather's protocol), so runs need no
+// barrier.  Empty blocks are skipped on both sides, both knowing the counts
+// (gatherv.cc:102: every rank holds the full list).
+// ---------------------------------------------------------------------------
+Plan planGather(int rank, int size, uint64_t count, const std::vector<int>& re) {
+  if (re.size() != 1 && (int)re.size() != 1 + size)
+    throw std::invalid_argument("gather: recv_elems has " + std::to_string(re.size()) + " entries; {root} or {root, " +
+                                std::to_string(size) + " per-rank counts} expected");
+  const int root = re[0];
+  if (root < 0 || root >= size)                                          // gather.cc:26
+    throw std::invalid_argument("gather: root rank " + std::to_string(root) + " outside [0, " + std::to_string(size) +
+                                ")");
+  for (int q = 1; q < (int)re.size(); q++)
+    if (re[q] < 0)
+      throw std::invalid_argument("gather: negative count " + std::to_string(re[q]) + " for rank " +
+                                  std::to_string(q - 1));
+  auto cnt = [&](int q) -> uint64_t { return re.size() == 1 ? count : (uint64_t)re[1 + q]; };
+  std::vector<uint64_t> off(size + 1, 0);
+  for (int q = 0; q < size; q++) off[q + 1] = off[q] + cnt(q);
+  Plan p;
+  if (off[size] == 0) return p;  // nothing to move
+  if (rank != root) {                                                    // gatherv.cc:101-106
+    if (cnt(rank) == 0) return p;
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, root, GLOO_HIP_SLOT_NOTIFY, GLOO_HIP_PREV_RUN));
+    p.steps.push_back(mk(GLOO_HIP_STEP_SEND, root, GLOO_HIP_SLOT_DATA0, GLOO_HIP_FROM_INPUTS, 0, 0, cnt(rank)));
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_SEND, root, GLOO_HIP_SLOT_DATA0));
+    return p;
+  }
+  std::vector<int> from;  // ascending rank, as the reference posts its receives (gatherv.cc:83-88)
+  for (int q = 0; q < size; q++)
+    if (q != rank && cnt(q) > 0) from.push_back(q);
+  if (size > 1) p.arena = off[size];
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, q, GLOO_HIP_SLOT_DATA0, 0, off[q], 0, cnt(q)));
+  if (cnt(rank) > 0)                                                     // gatherv.cc:89-93
+    p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_FROM_INPUTS, off[rank], 0, cnt(rank)));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, q, GLOO_HIP_SLOT_DATA0));  // :98-100
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, off[q], off[q], cnt(q)));
+  for (int q : from) p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY));
+  return p;
+}
+
+// ---------------------------------------------------------------------------
+// GLOO_HIP_ALGO_SCATTER: gloo::scatter (gloo/scatter.cc:19-61).  The root has
+// one input per destination rank, P separate buffers (:31-35); rank q's one
+// output ends with the root's input q.  Root: the sends to the peers in
+// ascending rank (:40-45), each after that peer's clear-to-send, the own
+// block input[root] -> output (:48), the send completions (:51-56).  Non-root:
+// clear-to-send, the arrival, the copy out of the inbox (:58-59; the
+// reference receives into the output itself).  As in the broadcast plan the
+// clear-to-send IS the credit: a receiver issues run r + 1's on its stream
+// after run r's COPY out of the inbox, so runs need no barrier.
+// Arena = [inbox: count] on a non-root rank, nothing on the root.
+// ---------------------------------------------------------------------------
+Plan planScatter(int rank, int size, uint64_t count, const std::vector<int>& re) {
+  if (re.size() != 1)
+    throw std::invalid_argument("scatter: recv_elems has " + std::to_string(re.size()) +
+                                " entries; {root} expected (there is no scatterv)");
+  const int root = re[0];
+  if (root < 0 || root >= size)                                          // scatter.cc:27
+    throw std::invalid_argument("scatter: root rank " + std::to_string(root) + " outside [0, " +
+                                std::to_string(size) + ")");
+  Plan p;
+  if (count == 0) return p;
+  if (rank != root) {
+    p.arena = count;
+    p.steps.push_back(mk(GLOO_HIP_STEP_DECL_RECV, root, GLOO_HIP_SLOT_DATA0, 0, 0, 0, count));
+    p.steps.push_back(mk(GLOO_HIP_STEP_NOTIFY, root, GLOO_HIP_SLOT_NOTIFY));
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_RECV, root, GLOO_HIP_SLOT_DATA0));
+    p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_SRC_ARENA, 0, 0, count));
+    return p;
+  }
+  for (int q = 0; q < size; q++) {
+    if (q == rank) continue;
+    p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_NOTIFY, q, GLOO_HIP_SLOT_NOTIFY));
+    p.steps.push_back(mk(GLOO_HIP_STEP_SEND, q, GLOO_HIP_SLOT_DATA0, GLOO_HIP_FROM_INPUTS | GLOO_HIP_INPUT(q), 0, 0,
+                         count));
+  }
+  p.steps.push_back(mk(GLOO_HIP_STEP_COPY, -1, 0, GLOO_HIP_FROM_INPUTS | GLOO_HIP_INPUT(rank), 0, 0, count));
+  for (int q = 0; q < size; q++)
+    if (q != rank) p.steps.push_back(mk(GLOO_HIP_STEP_WAIT_SEND, q, GLOO_HIP_SLOT_DATA0));
+  return p;
+}
+
 }  // namespace
+
+Plan makeGatherPlan(int algo, int rank, int size, uint64_t count, const std::vector<int>& recvElems) {
+  if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
+  // every block travels one hop already: there is nothing to derive
+  if (algo & GLOO_HIP_ALGO_MESH)
+    throw std::invalid_argument("gather has no mesh form: algorithm " + std::to_string(algo) +
+                                " (GLOO_HIP_ALGO_GATHER | GLOO_HIP_ALGO_MESH) is refused");
+  return planGather(rank, size, count, recvElems);
+}
+
+Plan makeScatterPlan(int algo, int rank, int size, uint64_t count, const std::vector<int>& recvElems) {
+  if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
+  if (algo & GLOO_HIP_ALGO_MESH)
+    throw std::invalid_argument("scatter has no mesh form: algorithm " + std::to_string(algo) +
+                                " (GLOO_HIP_ALGO_SCATTER | GLOO_HIP_ALGO_MESH) is refused");
+  return planScatter(rank, size, count, recvElems);
+}
 
 Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
@@ -1409,6 +1518,8 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
   if (nptrs < 1) throw std::invalid_argument("need at least one pointer");
   if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, 0, recvElems);  // in place
+  if (isGather(algo)) return makeGatherPlan(algo, rank, size, count, recvElems);
+  if (isScatter(algo)) return makeScatterPlan(algo, rank, size, count, recvElems);
   // (GLOO_HIP_ALGO_ALLTOALL is a planner only so far: gloo_hip_plan / gloo_hip_plan_ex build it, no
   // executor runs it, and it falls through to "unknown algorithm" here)
   if (algo & GLOO_HIP_ALGO_MESH) {
@@ -1462,6 +1573,12 @@ extern "C" int gloo_hip_plan(int algo, int rank, int size, size_t count, int npt
     }
     return gloo_hip_plan_ex(algo, rank, size, count, 1, 1, 4, 0, nullptr, steps, capacity, nsteps, arena_elems);
   }
+  if (gloo_amd::isRooted(algo) && recv_elems) {  // nptrs: the rank's pointers, {in[, out]} / {out[, in_0 ...]}
+    const bool root = recv_elems[0] == rank;
+    const bool gather = gloo_amd::isGather(algo);
+    return gloo_hip_plan_ex(algo, rank, size, count, gather ? 1 : root ? nptrs - 1 : 0, gather ? (root ? nptrs - 1 : 0) : 1,
+                            4, 0, recv_elems, steps, capacity, nsteps, arena_elems);
+  }
   return gloo_hip_plan_ex(algo, rank, size, count, 0, nptrs, 4, 0, recv_elems, steps, capacity, nsteps,
                           arena_elems);
 }
@@ -1487,6 +1604,28 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
       if (noutputs != 1) throw std::invalid_argument("alltoall has one output, not " + std::to_string(noutputs));
       if (recv_elems && size > 0) re.assign(recv_elems, recv_elems + 2 * size);
       p = gloo_amd::makeAlltoallPlan(algo, rank, size, count, ninputs, re);
+    } else if (gloo_amd::isRooted(algo)) {
+      // recv_elems: {root}, or for a gather with count == GLOO_HIP_COUNT_PER_RANK {root, c_0 ... c_{size-1}}
+      const bool gather = gloo_amd::isGather(algo);
+      const char* name = gather ? "gather" : "scatter";
+      if (!recv_elems) throw std::invalid_argument(std::string(name) + ": recv_elems is NULL ({root} expected)");
+      if (size < 1) throw std::invalid_argument("bad rank/size");
+      const bool perRank = gather && count == GLOO_HIP_COUNT_PER_RANK;
+      re.assign(recv_elems, recv_elems + (perRank ? 1 + size : 1));
+      const bool root = re[0] == rank;
+      if (gather) {
+        if (ninputs != 1) throw std::invalid_argument("gather has one input per rank, not " + std::to_string(ninputs));
+        if (root ? noutputs != 1 : (noutputs != 0 && noutputs != 1))
+          throw std::invalid_argument("gather: " + std::to_string(noutputs) + " outputs on rank " + std::to_string(rank) +
+                                      (root ? " (the root has one)" : " (a rank that is not the root has none)"));
+        p = gloo_amd::makeGatherPlan(algo, rank, size, perRank ? 0 : count, re);
+      } else {
+        if (noutputs != 1) throw std::invalid_argument("scatter has one output per rank, not " + std::to_string(noutputs));
+        if (root && re[0] >= 0 && re[0] < size && ninputs != size)
+          throw std::invalid_argument("scatter: the root has one input per rank (" + std::to_string(size) + "), not " +
+                                      std::to_string(ninputs));
+        p = gloo_amd::makeScatterPlan(algo, rank, size, count, re);
+      }
     } else if (gloo_amd::isNewStyle(algo)) {
       gloo_amd::NewStyleOptions o;
       o.ninputs = ninputs;

@@ -19,6 +19,14 @@
 //        gloo/allgatherv.cc:71-140) ->  gloo::hip::allgatherv(opts[, stream])
 //        (bytes only; every rank sends its block straight to every peer
 //        instead of round the reference's ring, the same bytes on every rank)
+//   gloo::gather(gloo::GatherOptions&)               (gloo/gather.h,
+//        gloo/gather.cc)            ->  gloo::hip::gather(opts[, stream])
+//   gloo::gatherv(gloo::GathervOptions&)             (gloo/gatherv.h,
+//        gloo/gatherv.cc:71-107)    ->  gloo::hip::gatherv(opts[, stream])
+//   gloo::scatter(gloo::ScatterOptions&)             (gloo/scatter.h,
+//        gloo/scatter.cc:19-61)     ->  gloo::hip::scatter(opts[, stream])
+//        (bytes only; the reference's own route, every block one hop to or
+//        from the root)
 //
 // The caller fills the SAME option object it would hand to gloo::allreduce /
 // gloo::reduce: setInput(s) / setOutput(s) with DEVICE pointers (the
@@ -58,8 +66,11 @@
 #include "gloo/allgatherv.h"
 #include "gloo/allreduce.h"
 #include "gloo/broadcast.h"
+#include "gloo/gather.h"
+#include "gloo/gatherv.h"
 #include "gloo/math.h"
 #include "gloo/reduce.h"
+#include "gloo/scatter.h"
 #include "gloo_amd/gloo_bridge.h"
 
 namespace gloo {
@@ -229,6 +240,55 @@ struct AllgathervAccess : ::gloo::AllgathervOptions {
   static uint32_t get_tag(const ::gloo::AllgathervOptions& o) { return o.*(&AllgathervAccess::tag); }
 };
 
+struct GatherAccess : ::gloo::GatherOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::GatherOptions& o) {
+    return o.*(&GatherAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::GatherOptions& o) {
+    return o.*(&GatherAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::GatherOptions& o) {
+    return o.*(&GatherAccess::out);
+  }
+  static size_t get_elementSize(const ::gloo::GatherOptions& o) { return o.*(&GatherAccess::elementSize); }
+  static int get_root(const ::gloo::GatherOptions& o) { return o.*(&GatherAccess::root); }
+  static uint32_t get_tag(const ::gloo::GatherOptions& o) { return o.*(&GatherAccess::tag); }
+};
+
+struct GathervAccess : ::gloo::GathervOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::GathervOptions& o) {
+    return o.*(&GathervAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::GathervOptions& o) {
+    return o.*(&GathervAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::GathervOptions& o) {
+    return o.*(&GathervAccess::out);
+  }
+  static const std::vector<size_t>& get_elementsPerRank(const ::gloo::GathervOptions& o) {
+    return o.*(&GathervAccess::elementsPerRank);
+  }
+  static size_t get_elementSize(const ::gloo::GathervOptions& o) { return o.*(&GathervAccess::elementSize); }
+  static int get_root(const ::gloo::GathervOptions& o) { return o.*(&GathervAccess::root); }
+  static uint32_t get_tag(const ::gloo::GathervOptions& o) { return o.*(&GathervAccess::tag); }
+};
+
+struct ScatterAccess : ::gloo::ScatterOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::ScatterOptions& o) {
+    return o.*(&ScatterAccess::context);
+  }
+  static const std::vector<std::unique_ptr<::gloo::transport::UnboundBuffer>>& get_in(
+      const ::gloo::ScatterOptions& o) {
+    return o.*(&ScatterAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::ScatterOptions& o) {
+    return o.*(&ScatterAccess::out);
+  }
+  static size_t get_elementSize(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::elementSize); }
+  static int get_root(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::root); }
+  static uint32_t get_tag(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::tag); }
+};
+
 }  // namespace detail
 
 // A CUSTOM reduce function for the new-style calls: `host` is what the
@@ -396,6 +456,102 @@ inline void allgatherv(::gloo::AllgathervOptions& opts, hipStream_t stream = nul
   g.tag = A::get_tag(opts);
   g.stream = stream;
   ::gloo::hip_bridge::check(gloo_hip_allgather(ctx, &g), "gloo::hip::allgatherv");
+}
+
+// gloo::gather(opts) (gloo/gather.cc) on device buffers: the root's output
+// receives rank 0's input, rank 1's input, ... back to back; a rank that is
+// not the root needs no output.  The options carry an element size and no
+// type, and a gather moves bytes, so the call goes down in uint8.
+inline void gather(::gloo::GatherOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::GatherAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_elementSize(opts) > 0);
+  GLOO_ENFORCE(A::get_in(opts), "no input buffer");
+  const int root = A::get_root(opts);
+  GLOO_ENFORCE(root >= 0 && root < ctxp->size);
+  const size_t inBytes = A::get_in(opts)->size;
+  if (ctxp->rank == root) {
+    GLOO_ENFORCE(A::get_out(opts), "no output buffer on the root");
+    GLOO_ENFORCE_EQ(A::get_out(opts)->size, inBytes * ctxp->size);
+  }
+  if (inBytes == 0) return;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, A::get_in(opts)->ptr);
+  gloo_hip_gather_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.root = root;
+  g.input = A::get_in(opts)->ptr;
+  g.output = ctxp->rank == root ? A::get_out(opts)->ptr : nullptr;
+  g.elements = inBytes;
+  g.counts = nullptr;
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_gather(ctx, &g), "gloo::hip::gather");
+}
+
+// gloo::gatherv(opts) (gloo/gatherv.cc:71-107): rank q contributes
+// elementsPerRank[q] elements, the root's output at their prefix offsets
+// (:82-96).
+inline void gatherv(::gloo::GathervOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::GathervAccess;
+  const auto& ctxp = A::get_context(opts);
+  const size_t es = A::get_elementSize(opts);
+  GLOO_ENFORCE(es > 0);                              // gloo/gatherv.cc:78
+  GLOO_ENFORCE(A::get_in(opts), "no input buffer");  // :79
+  const int root = A::get_root(opts);
+  GLOO_ENFORCE(root >= 0 && root < ctxp->size);
+  std::vector<size_t> bytes;
+  size_t total = 0;
+  for (size_t e : A::get_elementsPerRank(opts)) {
+    bytes.push_back(e * es);
+    total += e * es;
+  }
+  GLOO_ENFORCE_EQ(bytes.size(), (size_t)ctxp->size);
+  GLOO_ENFORCE_GE(A::get_in(opts)->size, bytes[ctxp->rank]);  // :103
+  if (ctxp->rank == root) GLOO_ENFORCE(A::get_out(opts), "no output buffer on the root");
+  if (total == 0) return;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, A::get_in(opts)->ptr);
+  gloo_hip_gather_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.root = root;
+  g.input = A::get_in(opts)->ptr;
+  g.output = ctxp->rank == root ? A::get_out(opts)->ptr : nullptr;
+  g.elements = 0;
+  g.counts = bytes.data();
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_gather(ctx, &g), "gloo::hip::gatherv");
+}
+
+// gloo::scatter(opts) (gloo/scatter.cc:19-61): rank q's output receives the
+// root's input q; the root's inputs are separate buffers (:31-35).
+inline void scatter(::gloo::ScatterOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::ScatterAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_elementSize(opts) > 0);  // gloo/scatter.cc:26
+  const int root = A::get_root(opts);
+  GLOO_ENFORCE(root >= 0 && root < ctxp->size);  // :27
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");  // :28
+  const size_t outBytes = A::get_out(opts)->size;
+  std::vector<void*> ins;
+  if (ctxp->rank == root) {
+    GLOO_ENFORCE_EQ(A::get_in(opts).size(), (size_t)ctxp->size);  // :31
+    for (const auto& b : A::get_in(opts)) {
+      GLOO_ENFORCE_EQ(b->size, outBytes);  // :34
+      ins.push_back(b->ptr);
+    }
+  }
+  if (outBytes == 0) return;
+  void* out = A::get_out(opts)->ptr;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, out);
+  gloo_hip_scatter_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.root = root;
+  g.output = out;
+  g.inputs = ctxp->rank == root ? ins.data() : nullptr;
+  g.elements = outBytes;
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_scatter(ctx, &g), "gloo::hip::scatter");
 }
 
 // Collective: tears down the library context (and its cached schedules)

@@ -534,4 +534,139 @@ inline void allgather(const AllgatherOptions& o) {
   exec.run();
 }
 
+// gloo::GatherOptions (gloo/gather.h) and gloo::GathervOptions
+// (gloo/gatherv.h) over device pointers, in one class: setOutput with one
+// element count (the whole output, a multiple of the ranks) is the former,
+// with per-rank counts the latter.  Only the root sets an output.
+class GatherOptions {
+ public:
+  explicit GatherOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInput(T* ptr, size_t elements) {
+    input_ = ptr;
+    inputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, size_t elements) {
+    output_ = ptr;
+    outputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, std::vector<size_t> counts) {
+    output_ = ptr;
+    counts_ = std::move(counts);
+    dtype_ = DType<T>::value;
+  }
+  // gatherv on a rank that is not the root: the counts without an output
+  void setCounts(std::vector<size_t> counts) { counts_ = std::move(counts); }
+  void setRoot(int root) { root_ = root; }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  void* input_ = nullptr;
+  void* output_ = nullptr;  // the root's; null elsewhere
+  size_t inputElements_ = 0, outputElements_ = 0;
+  std::vector<size_t> counts_;  // gatherv: elements per rank
+  int root_ = -1;
+  int dtype_ = GLOO_HIP_U8;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+using GathervOptions = GatherOptions;
+
+namespace detail {
+// A rank without an output hands the executor its input as the one pointer it
+// wants; no step of that rank's plan reads or writes output 0.
+inline void runGather(const GatherOptions& o, size_t count, const std::vector<int>& recvElems) {
+  const bool root = o.context_->rank == o.root_;
+  GLOO_AMD_ENFORCE(!root || o.output_, "gather: the root has no output");
+  PlanExecutor exec(o.context_, GLOO_HIP_ALGO_GATHER, GLOO_HIP_SUM /* not used */, o.dtype_,
+                    {root ? o.output_ : o.input_}, count, recvElems, o.stream_, {o.input_});
+  exec.run();
+}
+}  // namespace detail
+
+// gloo::gatherv(opts) (gloo/gatherv.cc:71-107): per-rank counts, the root's
+// output at their prefix offsets (:82-96).
+inline void gatherv(const GatherOptions& o) {
+  const int P = o.context_->size;
+  GLOO_AMD_ENFORCE(o.root_ >= 0 && o.root_ < P, "gatherv: root rank ", o.root_, " outside [0, ", P, ")");
+  GLOO_AMD_ENFORCE((int)o.counts_.size() == P, "gatherv: ", o.counts_.size(), " counts for ", P, " ranks");  // .cc:66
+  std::vector<int> re{o.root_};
+  size_t total = 0;
+  for (size_t c : o.counts_) {
+    GLOO_AMD_ENFORCE(c <= (size_t)INT32_MAX, "gatherv: count ", c, " is too large");
+    re.push_back((int)c);
+    total += c;
+  }
+  GLOO_AMD_ENFORCE(o.inputElements_ >= o.counts_[o.context_->rank], "gatherv: the input has ", o.inputElements_,
+                   " elements, this rank's count is ", o.counts_[o.context_->rank]);  // .cc:90, :103
+  if (total == 0) return;
+  detail::runGather(o, 0, re);
+}
+
+// gloo::gather(opts) (gloo/gather.cc): the same count on every rank.
+inline void gather(const GatherOptions& o) {
+  if (!o.counts_.empty()) return gatherv(o);
+  const size_t P = (size_t)o.context_->size;
+  GLOO_AMD_ENFORCE(o.root_ >= 0 && o.root_ < (int)P, "gather: root rank ", o.root_, " outside [0, ", P, ")");  // .cc:26
+  if (o.context_->rank == o.root_)
+    GLOO_AMD_ENFORCE(o.outputElements_ == o.inputElements_ * P, "gather: output of ", o.outputElements_,
+                     " elements, ", P, " inputs of ", o.inputElements_);  // .cc:32
+  if (o.inputElements_ == 0) return;
+  detail::runGather(o, o.inputElements_, {o.root_});
+}
+
+// gloo::ScatterOptions (gloo/scatter.h) over device pointers: the root sets
+// one input per rank (separate buffers, or slices of one allocation), every
+// rank one output of the same element count.
+class ScatterOptions {
+ public:
+  explicit ScatterOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInputs(std::vector<T*> ptrs, size_t elements) {
+    inputs_.assign(ptrs.begin(), ptrs.end());
+    inputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, size_t elements) {
+    output_ = ptr;
+    outputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  void setRoot(int root) { root_ = root; }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  std::vector<void*> inputs_;  // the root's; empty elsewhere
+  void* output_ = nullptr;
+  size_t inputElements_ = 0, outputElements_ = 0;
+  int root_ = -1;
+  int dtype_ = GLOO_HIP_U8;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+
+// gloo::scatter(opts) (gloo/scatter.cc:19-61).
+inline void scatter(const ScatterOptions& o) {
+  const int P = o.context_->size;
+  GLOO_AMD_ENFORCE(o.root_ >= 0 && o.root_ < P, "scatter: root rank ", o.root_, " outside [0, ", P, ")");  // .cc:27
+  GLOO_AMD_ENFORCE(o.output_ || o.outputElements_ == 0, "scatter: no output");                             // .cc:28
+  const bool root = o.context_->rank == o.root_;
+  if (root) {
+    GLOO_AMD_ENFORCE((int)o.inputs_.size() == P, "scatter: ", o.inputs_.size(), " inputs for ", P, " ranks");  // .cc:31
+    GLOO_AMD_ENFORCE(o.inputElements_ == o.outputElements_, "scatter: inputs of ", o.inputElements_,
+                     " elements, an output of ", o.outputElements_);  // .cc:34
+  }
+  if (o.outputElements_ == 0) return;
+  PlanExecutor exec(o.context_, GLOO_HIP_ALGO_SCATTER, GLOO_HIP_SUM /* not used */, o.dtype_, {o.output_},
+                    o.outputElements_, {o.root_}, o.stream_, root ? o.inputs_ : std::vector<void*>{});
+  exec.run();
+}
+
 }  // namespace gloo_amd

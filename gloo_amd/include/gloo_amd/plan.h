@@ -43,6 +43,19 @@ inline bool isAllgather(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_
 // != out_counts[rank] are refused.
 Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts);
 inline bool isAlltoall(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_ALLTOALL; }
+// GLOO_HIP_ALGO_GATHER (plan.cc planGather): one input per rank, one output
+// on the root.  recvElems = {root}: every block `count` elements; {root, c_0
+// ... c_{size-1}}: gatherv, `count` ignored.  Any other length, a root outside
+// [0, size), a negative count and algo | GLOO_HIP_ALGO_MESH are refused.  The
+// plan depends on nothing else, so every rank derives every peer's.
+Plan makeGatherPlan(int algo, int rank, int size, uint64_t count, const std::vector<int>& recvElems);
+inline bool isGather(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_GATHER; }
+// GLOO_HIP_ALGO_SCATTER (plan.cc planScatter): `size` inputs of `count`
+// elements on the root, one output per rank.  recvElems = {root}; any other
+// length, a root outside [0, size) and algo | GLOO_HIP_ALGO_MESH are refused.
+Plan makeScatterPlan(int algo, int rank, int size, uint64_t count, const std::vector<int>& recvElems);
+inline bool isScatter(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_SCATTER; }
+inline bool isRooted(int algo) { return isGather(algo) || isScatter(algo); }
 // Receives the text of a planner's refusal (an unknown algorithm, a mesh form
 // that does not exist, bad sizes) when gloo_hip_plan / gloo_hip_plan_ex return
 // GLOO_HIP_EINVAL_ARG.  The library installs its last-error text here

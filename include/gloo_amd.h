@@ -403,7 +403,79 @@ typedef enum {
    * sender writes one-sidedly, so an executor of this plan has to check
    * in_counts_q[r] == out_counts_r[q] for every pair before a byte moves. */
   GLOO_HIP_ALGO_ALLTOALL = 14,
+  /* gloo::gather and gloo::gatherv (gloo/gather.cc, gloo/gatherv.cc): every
+   * rank contributes ONE input of counts[rank] elements; afterwards the
+   * root's ONE output holds block 0, block 1, ... block P-1 back to back
+   * (gather.cc:40-47; gatherv.cc:82-96: prefix offsets).  A non-root rank has
+   * no output.  Not a reduction: op is NOT USED, dtype gives the element size.
+   *   recv_elems  is required.  {root}: the even form, `count` elements per
+   *          block.  {root, c_0 ... c_{P-1}}: gatherv, count ignored; every
+   *          rank passes the full list, as in the reference (gatherv.cc:102).
+   *          A C pointer carries no length, so gloo_hip_plan_ex and
+   *          gloo_hip_algorithm_create* read the second form exactly when
+   *          count == GLOO_HIP_COUNT_PER_RANK; gloo_hip_plan (the short form)
+   *          takes it the same way.
+   *   ptrs   at gloo_hip_algorithm_create*: {in} with nptrs = 1 on a rank
+   *          without an output, {in, out} with nptrs = 2 on the root.  A
+   *          non-root rank that passes a second pointer has it ignored (it
+   *          may be NULL).  In gloo_hip_plan_ex: ninputs = 1; noutputs = 1 on
+   *          the root, 0 ("no output") or 1 (ignored) elsewhere.
+   * Refused with GLOO_HIP_EINVAL_ARG before any exchange, the last-error text
+   * naming the value: a root outside [0, size), a negative count, a NULL
+   * recv_elems (a count list of the wrong length, where the length is known:
+   * gloo_amd::makeGatherPlan, gloo_amd.gather), ninputs != 1, a root without
+   * an output, | GLOO_HIP_ALGO_MESH.
+   * Route: the reference's own, every block straight to the root.
+   * Arena, on the root: laid out like the output, sum(counts) elements; the
+   * inbox for peer q is arena[offset(q), +c_q) on GLOO_HIP_SLOT_DATA0.
+   * Root order (peers in ascending rank, empty blocks skipped on both sides):
+   * DECL_RECVs; COPY | GLOO_HIP_FROM_INPUTS of the own block input -> output;
+   * WAIT_RECV per peer; COPY arena -> output per peer; NOTIFY per peer on
+   * GLOO_HIP_SLOT_NOTIFY (the credit: the block is out of the inbox).
+   * Non-root order: WAIT_NOTIFY | GLOO_HIP_PREV_RUN (the root's credit of the
+   * LAST run, met at once in the first); SEND | GLOO_HIP_FROM_INPUTS to the
+   * root; WAIT_SEND.  One rank: the COPY alone.  A total of 0: no steps.  The
+   * executor never promotes this plan.
+   * Streams: gloo_hip_algorithm_create_streams takes ONE stream (the plan's)
+   * or none for this algorithm and for GLOO_HIP_ALGO_SCATTER, whatever the
+   * rank's pointer count: that count differs between the root and the rest.
+   * Buffers: the root's input may BE its own slot of the output (in place:
+   * the COPY then moves nothing); otherwise no input may share a byte with
+   * the output. */
+  GLOO_HIP_ALGO_GATHER = 15,
+  /* gloo::scatter (gloo/scatter.cc): the root has P inputs of `count`
+   * elements, one per destination rank (P separate buffers, scatter.cc:31-35;
+   * they may be slices of one allocation); afterwards rank q's ONE output
+   * holds the root's input q.  There is no scatterv.  Not a reduction: op is
+   * NOT USED, dtype gives the element size.
+   *   recv_elems  is required: {root}.
+   *   ptrs   at gloo_hip_algorithm_create*: {out} with nptrs = 1 on a rank
+   *          that is not the root (further pointers are ignored), {out, in_0
+   *          ... in_{P-1}} with nptrs = 1 + size on the root.  In
+   *          gloo_hip_plan_ex: noutputs = 1; ninputs = size on the root, any
+   *          value elsewhere (0: none).
+   * Refused with GLOO_HIP_EINVAL_ARG before any exchange, naming the value: a
+   * root outside [0, size), a NULL recv_elems, noutputs != 1, a root whose
+   * ninputs is not size, | GLOO_HIP_ALGO_MESH.
+   * Arena: `count` elements on a non-root rank (its one inbox, from the root,
+   * on GLOO_HIP_SLOT_DATA0); nothing on the root.
+   * Root order: for each peer q in ascending rank WAIT_NOTIFY (its
+   * clear-to-send) then SEND | GLOO_HIP_FROM_INPUTS | GLOO_HIP_INPUT(q); COPY |
+   * GLOO_HIP_FROM_INPUTS | GLOO_HIP_INPUT(root) of the own block input ->
+   * output; WAIT_SEND per peer.  Non-root order: DECL_RECV; NOTIFY
+   * (clear-to-send, the broadcast's protocol); WAIT_RECV; COPY arena ->
+   * output.  One rank: the COPY alone; count 0: no steps.  The clear-to-send
+   * orders the root's next send after the receiver's copy out of its inbox,
+   * so runs need no barrier.  The executor never promotes this plan.
+   * Buffers: the root's output may BE its input `root` (in place); otherwise
+   * the output may share no byte with any input (the sends read the inputs
+   * while the own block is stored). */
+  GLOO_HIP_ALGO_SCATTER = 16,
 } gloo_hip_algo_t;
+
+/* GLOO_HIP_ALGO_GATHER: `count` of the gatherv form, recv_elems = {root, c_0 ...
+ * c_{size-1}} (a legitimate count never reaches it). */
+#define GLOO_HIP_COUNT_PER_RANK ((size_t)-1)
 
 /* algo | GLOO_HIP_ALGO_MESH: the algorithm's result with mesh data movement,
  * derived mechanically (gloo_amd/csrc/mesh.cc): every rank's plan is run
@@ -452,8 +524,17 @@ typedef enum {
  * outputs into output 0.  On REDUCE: user[dst] = input0[dst] op arena[src]
  * (gloo::reduce's out = in op tmp); on SEND: the source is input 0; on COPY
  * (GLOO_HIP_ALGO_ALLTOALL's own block, a plan no executor runs yet): the
- * source is input 0 as well, user[dst_off, +length) = input0[src_off, +length). */
+ * source is input 0 as well, user[dst_off, +length) = input0[src_off, +length).
+ * WHICH input a SEND or a COPY reads is in bits 8 and up of `flags`:
+ * GLOO_HIP_INPUT(q) names input q, GLOO_HIP_INPUT_OF(flags) reads it back.
+ * Every plan that knows one input leaves those bits 0 and so emits the steps
+ * it always did; GLOO_HIP_ALGO_SCATTER's root names input q for rank q
+ * (GLOO_HIP_ALGO_GATHER reads input 0).  The bits mean nothing without
+ * GLOO_HIP_FROM_INPUTS, and nothing on REDUCE, LOCAL_REDUCE and LOCAL_GATHER. */
 #define GLOO_HIP_FROM_INPUTS 4
+#define GLOO_HIP_INPUT_SHIFT 8
+#define GLOO_HIP_INPUT(q) ((int32_t)((uint32_t)(q) << GLOO_HIP_INPUT_SHIFT))
+#define GLOO_HIP_INPUT_OF(flags) ((int)((uint32_t)(flags) >> GLOO_HIP_INPUT_SHIFT))
 /* FOLD: each new source is the LEFT operand (acc = s_k op acc). */
 #define GLOO_HIP_FOLD_REVERSE 8
 /* FOLD: balanced pairwise tree over the sources in order (k a power of two):
@@ -636,7 +717,7 @@ int gloo_hip_algorithm_stats(gloo_hip_algorithm_t algo, double* stats4);
 int gloo_hip_algorithm_mode(gloo_hip_algorithm_t algo, int* mode4);
 /* The same for the schedule that ran the latest function-style call
  * (gloo_hip_allreduce / gloo_hip_reduce_to_root / gloo_hip_broadcast /
- * gloo_hip_allgather) on `ctx`. */
+ * gloo_hip_allgather / gloo_hip_gather / gloo_hip_scatter) on `ctx`. */
 int gloo_hip_context_mode(gloo_hip_context_t ctx, int* mode4);
 
 /* ------------------------------------------------------------------------
@@ -738,6 +819,56 @@ typedef struct {
 } gloo_hip_allgather_options_t;
 
 int gloo_hip_allgather(gloo_hip_context_t ctx, const gloo_hip_allgather_options_t* opts);
+
+/* ------------------------------------------------------------------------
+ * New-style function API: gloo::gather(GatherOptions&) (gloo/gather.h,
+ * gloo/gather.cc) and gloo::gatherv (gloo/gatherv.h, gloo/gatherv.cc) in one
+ * call: afterwards `output` on the ROOT holds rank 0's input, rank 1's input,
+ * ... back to back (`elements` each, or counts[r] with counts given:
+ * gatherv's prefix offsets, gatherv.cc:82-96).  A rank that is not the root
+ * has no output: it leaves `output` NULL (a pointer given there is ignored and
+ * never written).  Every rank passes the same root, elements and counts (the
+ * full list, gatherv.cc:102).  Runs GLOO_HIP_ALGO_GATHER.  Collective, cached
+ * per option set (dtype, counts, root, tag) like gloo_hip_allgather;
+ * gloo_hip_context_mode reports the schedule that ran.  A bad dtype, a root
+ * outside [0, size), a count above INT32_MAX, a NULL input with elements to
+ * send and a NULL output on the root are refused before any exchange.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int dtype;                /* gloo_hip_dtype_t                                      */
+  int root;                 /* setRoot                                               */
+  void* input;              /* device pointer, this rank's block                     */
+  void* output;             /* root: device pointer, the sum of the counts; else NULL */
+  size_t elements;          /* per rank; ignored when counts is given                */
+  const size_t* counts;     /* NULL: `elements` on every rank; else `size` entries   */
+  uint32_t tag;             /* setTag                                                */
+  gloo_hip_stream_t stream; /* NULL: the output is complete on return                */
+} gloo_hip_gather_options_t;
+
+int gloo_hip_gather(gloo_hip_context_t ctx, const gloo_hip_gather_options_t* opts);
+
+/* ------------------------------------------------------------------------
+ * New-style function API: gloo::scatter(ScatterOptions&) (gloo/scatter.h,
+ * gloo/scatter.cc): afterwards `output` on rank q holds the root's inputs[q],
+ * `elements` elements.  inputs is a HOST array of `size` device pointers that
+ * the root alone sets (P separate buffers, scatter.cc:31-35; they may be
+ * slices of one allocation); every other rank leaves it NULL (it is not read
+ * there).  Runs GLOO_HIP_ALGO_SCATTER.  Collective, cached per option set
+ * (dtype, elements, root, tag).  A bad dtype, a root outside [0, size), a NULL
+ * output and, on the root, a NULL inputs array or entry are refused before
+ * any exchange.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int dtype;                /* gloo_hip_dtype_t                                      */
+  int root;                 /* setRoot                                               */
+  void* output;             /* device pointer, `elements` elements                   */
+  void* const* inputs;      /* root: host array of `size` device pointers; else NULL */
+  size_t elements;          /* per rank                                              */
+  uint32_t tag;             /* setTag                                                */
+  gloo_hip_stream_t stream; /* NULL: the output is complete on return                */
+} gloo_hip_scatter_options_t;
+
+int gloo_hip_scatter(gloo_hip_context_t ctx, const gloo_hip_scatter_options_t* opts);
 
 /* ------------------------------------------------------------------------
  * The xGMI transport: bound buffers of gloo::transport::Pair / Buffer
