@@ -59,7 +59,20 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
             "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
-            "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel")
+            "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel",
+            "gloo_hip_interp_kernel", "gloo_hip_fused_step")
+MAX_SRCS, MAX_XDSTS = 8, 8  # include/gloo_amd.h GLOO_HIP_MAX_SRCS, GLOO_HIP_MAX_XDSTS
+
+
+class InterpStep(ctypes.Structure):
+    """gloo_hip_interp_step_t: one step of gloo_hip_interp_kernel's list."""
+    _fields_ = [("kind", ctypes.c_int32), ("mode", ctypes.c_int32), ("nsrc", ctypes.c_int32), ("defer", ctypes.c_int32),
+                ("flag", ctypes.c_void_p), ("base", ctypes.c_uint64), ("per_run", ctypes.c_uint64),
+                ("dst", ctypes.c_void_p), ("src", ctypes.c_void_p * MAX_SRCS), ("n", ctypes.c_uint64),
+                ("nxdst", ctypes.c_int32), ("reserved", ctypes.c_int32), ("xdst", ctypes.c_void_p * MAX_XDSTS)]
+
+
+INTERP_COPY, INTERP_SEND, INTERP_SIGNAL, INTERP_WAIT, INTERP_FOLD = range(5)
 
 
 class GlooHipError(RuntimeError):
@@ -99,6 +112,11 @@ def _load():
     L.gloo_hip_fold_kernel.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp), ctypes.c_int, sz, ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint64),
                                        ctypes.c_int, vp, vp]
+    u64 = ctypes.c_uint64
+    L.gloo_hip_interp_kernel.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(InterpStep), ctypes.c_int, u64,
+                                         ctypes.c_int, u64, vp, vp, vp, vp]
+    L.gloo_hip_fused_step.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, sz, vp, u64, u64, u64, vp, vp, u64, u64, vp,
+                                      vp]
     return L
 
 
@@ -214,6 +232,47 @@ def fold_kernel(op, dtype, dst, srcs, n, mode=0, fwd=(), fwd_flags=None, fwd_val
     _check(lib.gloo_hip_fold_kernel(_as_op(op), _as_dtype(dtype), dst, (vp * k)(*srcs), k, n, mode,
                                     (vp * nf)(*[p or None for p in fwd]) if nf else None, flags, values, nf,
                                     ticket or None, stream or None))
+
+
+def interp_step(kind, dst=0, src=(), n=0, mode=0, flag=0, base=0, per_run=0, xdst=(), defer=0, nsrc=None,
+                nxdst=None):
+    """One gloo_hip_interp_step_t.  kind: INTERP_COPY / SEND / SIGNAL / WAIT /
+    FOLD; src: the sources (one for a copy or a send); xdst: a copy's further
+    destinations; nsrc / nxdst: the counts, when they are not the lengths."""
+    t = InterpStep()
+    t.kind, t.mode, t.defer = int(kind), int(mode), int(defer)
+    t.nsrc = len(src) if nsrc is None else int(nsrc)
+    t.flag, t.base, t.per_run = flag or None, int(base) & (2 ** 64 - 1), int(per_run) & (2 ** 64 - 1)
+    t.dst, t.n = dst or None, int(n)
+    for j, p in enumerate(src):
+        t.src[j] = p or None
+    t.nxdst = len(xdst) if nxdst is None else int(nxdst)
+    for r, p in enumerate(xdst):
+        t.xdst[r] = p or None
+    return t
+
+
+def interp_kernel(op, dtype, steps, err, run=1, slices=1, timeout_ticks=10 ** 7, done=0, done_ticket=0, stream=0):
+    """gloo_hip_interp_kernel: the one-launch plan interpreter on a list of
+    interp_step()s, `slices` workgroups; synchronous (the stream is
+    synchronised before it returns).  err: a device uint32 a timed-out wait
+    sets; done / done_ticket: the completion words (both or neither)."""
+    n = len(steps)
+    arr = (InterpStep * n)(*steps) if n else None
+    _check(lib.gloo_hip_interp_kernel(_as_op(op), _as_dtype(dtype), arr, n, int(run) & (2 ** 64 - 1), slices,
+                                      timeout_ticks, err or None, done or None, done_ticket or None, stream or None))
+
+
+def fused_step(op, dtype, dst, src, n, err, wait_flag=0, wait_base=0, wait_per_run=0, sig_flag=0, sig_base=0,
+               sig_per_run=0, epoch=0, timeout_ticks=10 ** 7, stream=0):
+    """gloo_hip_fused_step: [wait] -> dst op= src (op 0 / None: copy) ->
+    [signal] in one one-workgroup launch, asynchronous on `stream`.  A value
+    is base + *epoch * per_run (epoch: a device word, 0 for none)."""
+    m = 2 ** 64 - 1
+    _check(lib.gloo_hip_fused_step(_as_op(op) if op else 0, _as_dtype(dtype), dst or None, src or None, n,
+                                   wait_flag or None, int(wait_base) & m, int(wait_per_run) & m, timeout_ticks,
+                                   err or None, sig_flag or None, int(sig_base) & m, int(sig_per_run) & m,
+                                   epoch or None, stream or None))
 
 
 def set_variant(v):

@@ -2094,6 +2094,142 @@ int gloo_hip_fold_kernel(int op, int dtype, void* dst, const void* const* srcs, 
   return launchFoldSend(op, dtype, dst, srcs, k, n, mode, d, nfwd, ticket, nullptr, static_cast<hipStream_t>(stream));
 }
 
+// 10 s of the 100 MHz clock: the longest a test entry's wait may spin
+static constexpr uint64_t kMaxTestTimeoutTicks = 1000000000ull;
+
+static int checkTestTimeout(const char* who, uint64_t ticks) {
+  if (ticks >= 1 && ticks <= kMaxTestTimeoutTicks) return GLOO_HIP_OK;
+  return setError(GLOO_HIP_EINVAL_ARG, std::string(who) + ": timeout_ticks " + std::to_string(ticks) +
+                                           " outside [1, 1000000000]");
+}
+
+static bool rangesOverlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+
+int gloo_hip_interp_kernel(int op, int dtype, const gloo_hip_interp_step_t* steps, int nsteps, uint64_t run,
+                           int slices, uint64_t timeout_ticks, uint32_t* err, uint64_t* done, unsigned* done_ticket,
+                           gloo_hip_stream_t stream) {
+  static_assert(sizeof(gloo_hip_interp_step_t) == sizeof(InterpStep), "the public step mirrors InterpStep");
+  static_assert(GLOO_HIP_MAX_XDSTS == kMaxCopyEntries, "InterpStep holds kMaxCopyEntries extra destinations");
+  auto bad = [](int code, int i, const std::string& what) {
+    return setError(code, "interpreter step " + std::to_string(i) + ": " + what);
+  };
+  if (nsteps < 0 || nsteps > kInterpMaxSteps)
+    return setError(GLOO_HIP_EINVAL_ARG, "interpreter: step count " + std::to_string(nsteps) + " outside [0, " +
+                                             std::to_string(kInterpMaxSteps) + "]");
+  if (nsteps > 0 && !steps) return set_error(GLOO_HIP_EINVAL_PTR, "interpreter: null step list");
+  if (slices < 1 || slices > kMaxSlices)
+    return setError(GLOO_HIP_EINVAL_ARG, "interpreter: slice count " + std::to_string(slices) + " outside [1, " +
+                                             std::to_string(kMaxSlices) + "]");
+  if (!err) return set_error(GLOO_HIP_EINVAL_PTR, "interpreter: null err word");
+  if ((done == nullptr) != (done_ticket == nullptr))
+    return set_error(GLOO_HIP_EINVAL_ARG, "interpreter: half a done signal (done and done_ticket go together)");
+  if (const int rc = checkTestTimeout("interpreter", timeout_ticks)) return rc;
+  const size_t es = gloo_hip_dtype_size(dtype);
+  if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+  if (!isBuiltinOp(op, dtype)) return set_error(GLOO_HIP_EINVAL_OP, "the interpreter takes a built-in op");
+  std::vector<InterpStep> v((size_t)nsteps);
+  for (int i = 0; i < nsteps; i++) {
+    const gloo_hip_interp_step_t& s = steps[i];
+    InterpStep& t = v[(size_t)i];
+    memset(&t, 0, sizeof t);
+    if (s.kind < kInterpCopy || s.kind > kInterpFold) return bad(GLOO_HIP_EINVAL_ARG, i, "unknown kind " + std::to_string(s.kind));
+    const bool fold = s.kind == kInterpFold, moves = s.kind == kInterpCopy || s.kind == kInterpSend;
+    if (s.mode < 0 || s.mode > 2) return bad(GLOO_HIP_EINVAL_ARG, i, "unknown fold mode " + std::to_string(s.mode));
+    if (fold && (s.nsrc < 1 || s.nsrc > GLOO_HIP_MAX_SRCS))
+      return bad(GLOO_HIP_EINVAL_ARG, i, "source count " + std::to_string(s.nsrc) + " outside [1, 8]");
+    if (fold && s.mode == 2 && (s.nsrc & (s.nsrc - 1)))
+      return bad(GLOO_HIP_EINVAL_ARG, i, "tree fold needs a power-of-two count, not " + std::to_string(s.nsrc));
+    if (s.defer != 0 && s.defer != 1) return bad(GLOO_HIP_EINVAL_ARG, i, "defer bit " + std::to_string(s.defer));
+    if (s.defer && i == nsteps - 1) return bad(GLOO_HIP_EINVAL_ARG, i, "defer bit on the last step");
+    if (s.defer && (s.kind == kInterpWait) != (steps[i + 1].kind == kInterpWait))
+      return bad(GLOO_HIP_EINVAL_ARG, i, "defer bit joins a wait and a step that is none");
+    if (s.kind != kInterpCopy && s.kind != kInterpFold && !s.flag) return bad(GLOO_HIP_EINVAL_PTR, i, "null flag");
+    if (s.nxdst < 0 || s.nxdst > GLOO_HIP_MAX_XDSTS)
+      return bad(GLOO_HIP_EINVAL_ARG, i, "extra destination count " + std::to_string(s.nxdst) + " outside [0, 8]");
+    if (s.nxdst && s.kind != kInterpCopy) return bad(GLOO_HIP_EINVAL_ARG, i, "extra destinations on a step that is no COPY");
+    const int ns = fold ? s.nsrc : 1;
+    if ((fold || moves) && s.n > 0) {
+      if (s.n > ((uint64_t)1 << 40)) return bad(GLOO_HIP_EINVAL_ARG, i, "n " + std::to_string(s.n) + " too large");
+      const uint64_t bytes = s.n * es;
+      if (!s.dst) return bad(GLOO_HIP_EINVAL_PTR, i, "null dst pointer");
+      if ((uintptr_t)s.dst % es) return bad(GLOO_HIP_EINVAL_PTR, i, "dst not aligned to the element size");
+      for (int j = 0; j < ns; j++) {
+        if (!s.src[j]) return bad(GLOO_HIP_EINVAL_PTR, i, "null source pointer " + std::to_string(j));
+        if ((uintptr_t)s.src[j] % es)
+          return bad(GLOO_HIP_EINVAL_PTR, i, "source " + std::to_string(j) + " not aligned to the element size");
+      }
+      if (moves && rangesOverlap(s.dst, s.src[0], bytes)) return bad(GLOO_HIP_EINVAL_ARG, i, "source overlaps dst");
+      for (int r = 0; r < s.nxdst; r++) {
+        if (!s.xdst[r]) return bad(GLOO_HIP_EINVAL_PTR, i, "null extra destination " + std::to_string(r));
+        if ((uintptr_t)s.xdst[r] % es)
+          return bad(GLOO_HIP_EINVAL_PTR, i, "extra destination " + std::to_string(r) + " not aligned to the element size");
+        if (rangesOverlap(s.xdst[r], s.src[0], bytes))
+          return bad(GLOO_HIP_EINVAL_ARG, i, "source overlaps extra destination " + std::to_string(r));
+      }
+    }
+    t.kind = s.kind;
+    t.mode = fold ? s.mode : 0;
+    t.nsrc = ns;
+    t.flags = s.defer ? kInterpDefer : 0;
+    t.flag = s.flag;
+    t.base = s.base;
+    t.perRun = s.per_run;
+    if (fold || moves) {
+      t.dst = static_cast<char*>(s.dst);
+      for (int j = 0; j < ns; j++) t.src[j] = static_cast<const char*>(s.src[j]);
+      t.n = s.n;
+      t.nxdst = s.nxdst;
+      for (int r = 0; r < s.nxdst; r++) t.xdst[r] = static_cast<char*>(s.xdst[r]);
+    }
+  }
+  if (nsteps == 0) return GLOO_HIP_OK;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  InterpStep* dev = nullptr;
+  const size_t bytes = v.size() * sizeof(InterpStep);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), bytes);
+  if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+  int rc = GLOO_HIP_OK;
+  e = hipMemcpyAsync(dev, v.data(), bytes, hipMemcpyHostToDevice, hs);
+  if (e == hipSuccess) {
+    rc = launchPlanInterp(op, dtype, dev, nsteps, run, timeout_ticks, err, slices, hs, done, done_ticket);
+    e = hipStreamSynchronize(hs);  // the staging outlives the launch: a synchronous entry
+  }
+  const hipError_t ef = hipFree(dev);
+  if (rc != GLOO_HIP_OK) return rc;
+  if (e == hipSuccess) e = ef;
+  if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+  return GLOO_HIP_OK;
+}
+
+int gloo_hip_fused_step(int op, int dtype, void* dst, const void* src, size_t n, const uint64_t* wait_flag,
+                        uint64_t wait_base, uint64_t wait_per_run, uint64_t timeout_ticks, uint32_t* err,
+                        uint64_t* sig_flag, uint64_t sig_base, uint64_t sig_per_run, const uint64_t* epoch,
+                        gloo_hip_stream_t stream) {
+  const size_t es = gloo_hip_dtype_size(dtype);
+  if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
+  if (op != 0) {  // 0: copy
+    if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+    if (!isBuiltinOp(op, dtype)) return set_error(GLOO_HIP_EINVAL_OP, "the fused step takes a built-in op or 0 (copy)");
+  }
+  if (!err) return set_error(GLOO_HIP_EINVAL_PTR, "fused step: null err word");
+  if (const int rc = checkTestTimeout("fused step", timeout_ticks)) return rc;
+  if (n > 0) {
+    if (n > ((size_t)1 << 40)) return setError(GLOO_HIP_EINVAL_ARG, "fused step: n " + std::to_string(n) + " too large");
+    if (!dst) return set_error(GLOO_HIP_EINVAL_PTR, "fused step: null dst pointer");
+    if ((uintptr_t)dst % es) return set_error(GLOO_HIP_EINVAL_PTR, "fused step: dst not aligned to the element size");
+    if (!src) return set_error(GLOO_HIP_EINVAL_PTR, "fused step: null source pointer");
+    if ((uintptr_t)src % es) return set_error(GLOO_HIP_EINVAL_PTR, "fused step: source not aligned to the element size");
+    if (rangesOverlap(dst, src, n * es)) return set_error(GLOO_HIP_EINVAL_ARG, "fused step: source overlaps dst");
+  }
+  if (n == 0 && !wait_flag && !sig_flag) return GLOO_HIP_OK;
+  return launchFusedSmall(op, dtype, dst, src, n, wait_flag, Seq{wait_base, wait_per_run}, timeout_ticks, err, sig_flag,
+                          Seq{sig_base, sig_per_run}, epoch, static_cast<hipStream_t>(stream));
+}
+
 int gloo_hip_register_op(gloo_hip_custom_fn fn, void* user, int* op_out) {
   if (!fn || !op_out) return set_error(GLOO_HIP_EINVAL_ARG, "null argument");
   std::lock_guard<std::mutex> lk(customMutex());

@@ -598,6 +598,57 @@ typedef struct {
 } gloo_hip_interp_desc_ex_t;
 int gloo_hip_interp_batches_ex(const gloo_hip_interp_desc_ex_t* steps, int n, int* defer_out);
 
+/* (new, tests) The one-launch plan interpreter (reduce.hip plan_interp_kernel)
+ * on a caller's step list, without a peer.  One step: */
+typedef struct {
+  int32_t kind;    /* 0 copy, 1 send, 2 signal, 3 wait, 4 fold (as gloo_hip_interp_desc_t) */
+  int32_t mode;    /* fold: 0 left (acc = acc op s_j), 1 reverse (acc = s_j op acc), 2 balanced tree */
+  int32_t nsrc;    /* fold: sources, 1..GLOO_HIP_MAX_SRCS (a power of two under mode 2); copy / send: src[0] */
+  int32_t defer;   /* 1: this step and the next share one drain (gloo_hip_interp_batches_ex) */
+  uint64_t* flag;  /* send / signal: slice g stores base + run * per_run (mod 2^64) to flag[g]; wait: polls flag[g] */
+  uint64_t base, per_run;
+  void* dst;
+  const void* src[GLOO_HIP_MAX_SRCS];
+  uint64_t n;      /* elements of `dtype` */
+  int32_t nxdst;   /* copy: further destinations of the same bytes */
+  int32_t reserved; /* 0 */
+  void* xdst[GLOO_HIP_MAX_XDSTS];
+} gloo_hip_interp_step_t;
+/* steps: a HOST array of nsteps <= 512 steps.  The entry stages it in device
+ * memory of its own, launches `slices` (1..256) workgroups on `stream` —
+ * workgroup g takes elements [min(n, g q), min(n, g q + q)) of every data
+ * step, q = ceil(n / slices) rounded up to 16 bytes, and flag word g —
+ * SYNCHRONISES the stream and frees the staging: a synchronous test entry,
+ * not a hot path.  A wait is met by signed 64-bit difference (a target below
+ * the counter passes at once); one that is not met within timeout_ticks
+ * (1..10^9 ticks of the 100 MHz clock, 10 s at the most) stores 1 to *err and
+ * ends its workgroup: no later step, no later flag, no done.  done /
+ * done_ticket (both or neither; the ticket a zeroed device word): the
+ * workgroup finishing last stores `run` to *done and leaves the ticket at 0.
+ * Built-in ops only.  Every argument and every step is checked before any
+ * GPU call (the last-error text names the step and the value): kind, mode,
+ * nsrc, the defer bit (0 / 1, never on the last step, never between a wait
+ * and a step that is none), a flag on send / signal / wait, and with n > 0
+ * non-null element-aligned dst, sources and extra destinations, a copy's or
+ * send's source disjoint from its destinations, nxdst 0..8 and 0 on every
+ * kind but copy.  nsteps == 0 launches nothing. */
+int gloo_hip_interp_kernel(int op, int dtype, const gloo_hip_interp_step_t* steps, int nsteps, uint64_t run,
+                           int slices, uint64_t timeout_ticks, uint32_t* err, uint64_t* done, unsigned* done_ticket,
+                           gloo_hip_stream_t stream);
+
+/* (new, tests) The fused small step (reduce.hip fused_small_kernel), one
+ * workgroup: [wait until *wait_flag >= wait value, by signed difference] ->
+ * dst[i] = dst[i] op src[i], i < n (op 0: dst[i] = src[i]) -> [*sig_flag =
+ * signal value].  A value is base + *epoch * per_run (mod 2^64), or base with
+ * epoch == NULL (epoch: a device word).  A wait not met within timeout_ticks
+ * (1..10^9) stores 1 to *err (never NULL): no work, no signal.  dst and src
+ * are element-aligned and disjoint.  Asynchronous on `stream`; every argument
+ * is checked before any GPU call; n == 0 without a flag launches nothing. */
+int gloo_hip_fused_step(int op, int dtype, void* dst, const void* src, size_t n, const uint64_t* wait_flag,
+                        uint64_t wait_base, uint64_t wait_per_run, uint64_t timeout_ticks, uint32_t* err,
+                        uint64_t* sig_flag, uint64_t sig_base, uint64_t sig_per_run, const uint64_t* epoch,
+                        gloo_hip_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Contexts and algorithms (the GPU allreduce / reduce-scatter drop-ins).
  *
