@@ -835,3 +835,105 @@ def scatter(ctx, output, elements, dtype, root, inputs=None, tag=0, stream=0):
     o.tag = tag
     o.stream = stream or None
     _check(lib.gloo_hip_scatter(ctx._h, ctypes.byref(o)))
+
+
+# ---- gloo::alltoall(opts) / gloo::alltoallv(opts) ----------------------------
+
+class AlltoallOptions(ctypes.Structure):
+    """gloo_hip_alltoall_options_t (mirrors gloo::AlltoallOptions, gloo/alltoall.h,
+    and gloo::AlltoallvOptions, gloo/alltoallv.h)."""
+    _fields_ = [("dtype", ctypes.c_int), ("input", ctypes.c_void_p), ("output", ctypes.c_void_p),
+                ("elements", ctypes.c_size_t), ("in_counts", ctypes.POINTER(ctypes.c_size_t)),
+                ("out_counts", ctypes.POINTER(ctypes.c_size_t)), ("matrix", ctypes.POINTER(ctypes.c_size_t)),
+                ("tag", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
+lib.gloo_hip_alltoall.argtypes = [ctypes.c_void_p, ctypes.POINTER(AlltoallOptions)]
+lib.gloo_hip_alltoall_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_void_p)]
+lib.gloo_hip_alltoall_lists.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int)]
+EXPORTED = EXPORTED + ("gloo_hip_alltoall", "gloo_hip_alltoall_create", "gloo_hip_alltoall_lists")
+
+
+def _flat_matrix(name, ctx, matrix):
+    """A P x P count matrix, nested or flat, as a flat list of ints."""
+    m = [int(x) for row in matrix for x in row] if len(matrix) and hasattr(matrix[0], "__len__") else \
+        [int(x) for x in matrix]
+    if len(m) != ctx.size * ctx.size:
+        raise GlooHipError(1, f"{name}: a count matrix of {len(m)} entries for {ctx.size} ranks "
+                              f"({ctx.size * ctx.size} expected)")
+    for k, c in enumerate(m):
+        if c < 0:
+            raise GlooHipError(1, f"{name}: negative count {c} from rank {k // ctx.size} to rank {k % ctx.size}")
+    return m
+
+
+def alltoall(ctx, input, output, elements, dtype, in_counts=None, out_counts=None, matrix=None, tag=0, stream=0):
+    """gloo::alltoall(opts) / gloo::alltoallv(opts) on device pointers
+    (GLOO_HIP_ALGO_ALLTOALL): afterwards block q of this rank's output holds
+    block `rank` of rank q's input.  Three forms (include/gloo_amd.h): even
+    (`elements` per block); matrix (matrix[q][r] elements from rank q to rank
+    r, the same on every rank; elements is ignored); own lists (in_counts[q]
+    elements for rank q and out_counts[q] from rank q, both given), which
+    costs one host exchange of the counts on EVERY call.  Input and output may
+    share no byte."""
+    o = AlltoallOptions()
+    o.dtype = _as_dtype(dtype)
+    o.input = input or None
+    o.output = output or None
+    o.elements = int(elements)
+    keep = []
+    for name, counts in (("in_counts", in_counts), ("out_counts", out_counts)):
+        if counts is None:
+            continue
+        if len(counts) != ctx.size:
+            raise GlooHipError(1, f"alltoall: {len(counts)} {name} for {ctx.size} ranks")
+        for q, c in enumerate(counts):
+            if int(c) < 0:
+                raise GlooHipError(1, f"alltoall: negative {name[:-1]} {int(c)} for rank {q}")
+        arr = (ctypes.c_size_t * len(counts))(*[int(c) for c in counts])
+        keep.append(arr)
+        setattr(o, name, ctypes.cast(arr, ctypes.POINTER(ctypes.c_size_t)))
+    if matrix is not None:
+        m = _flat_matrix("alltoall", ctx, matrix)
+        arr = (ctypes.c_size_t * len(m))(*m)
+        keep.append(arr)
+        o.matrix = ctypes.cast(arr, ctypes.POINTER(ctypes.c_size_t))
+    o.tag = tag
+    o.stream = stream or None
+    _check(lib.gloo_hip_alltoall(ctx._h, ctypes.byref(o)))
+
+
+class Alltoall(Algorithm):
+    """The algorithm-object form of an alltoall (gloo_hip_alltoall_create):
+    create once, run() many times; Algorithm's run / mode / stats / close
+    apply.  matrix None: `count` elements per block; else matrix[q][r]
+    elements from rank q to rank r, the same on every rank (count is ignored).
+    Algorithm(ctx, 14, ...) stays refused: an alltoall's pointers and matrix do
+    not fit that signature."""
+
+    def __init__(self, ctx, dtype, input, output, count=0, matrix=None, stream=0, workspace="device"):
+        self.ctx = ctx
+        self._h = None
+        mp = None
+        if matrix is not None:
+            m = _flat_matrix("alltoall", ctx, matrix)
+            mp = (ctypes.c_int * len(m))(*m)
+        h = ctypes.c_void_p()
+        ws = WORKSPACES[workspace] if isinstance(workspace, str) else int(workspace)
+        _check(lib.gloo_hip_alltoall_create(ctx._h, _as_dtype(dtype), input or None, output or None, int(count), mp,
+                                            stream or None, ws, ctypes.byref(h)))
+        self._h = h
+
+
+def alltoall_lists(rank, size, matrix):
+    """Row `rank` then column `rank` of a size x size count matrix (flat): the
+    recv_elems of gloo_hip_plan_ex for that rank (gloo_hip_alltoall_lists)."""
+    m = (ctypes.c_int * len(matrix))(*[int(x) for x in matrix])
+    if len(matrix) != size * size:
+        raise GlooHipError(1, f"alltoall_lists: {len(matrix)} entries for {size} ranks")
+    out = (ctypes.c_int * (2 * size))()
+    _check(lib.gloo_hip_alltoall_lists(rank, size, m, out))
+    return list(out)

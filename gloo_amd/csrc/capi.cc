@@ -162,6 +162,50 @@ void rootedArgs(int algo, int rank, int size, void* const* ptrs, int nptrs, size
   }
   *op = GLOO_HIP_SUM;
 }
+
+// GLOO_HIP_ALGO_ALLTOALL at the generic algorithm entry points: refused, as
+// before there was an executor for it.  An alltoall's pointers ({input,
+// output}, neither of them a list) and its P x P count matrix do not fit that
+// signature; gloo_hip_alltoall_create is its algorithm-object form.
+void refuseAlltoall(int algo) {
+  GLOO_AMD_ENFORCE(!gloo_amd::isAlltoall(algo), "unknown algorithm ", algo,
+                   " at this entry point (an alltoall's {input, output} and count matrix do not fit its signature: "
+                   "gloo_hip_alltoall_create)");
+}
+
+// What both alltoall entries check on this rank before any exchange with a
+// peer, given the rank's lists (`lists` empty: the even form of `count`
+// elements per block; else in_counts then out_counts, 2 * size ints): the
+// planner's own refusals (the rank's plan is built once for them), a NULL
+// buffer where there are elements to move, and an input that shares a byte
+// with the output (there is no in-place form: the sends read the input while
+// the own block and the copy-outs store the output).
+void alltoallBuffers(int rank, int size, int dtype, size_t count, const std::vector<int>& lists, const void* input,
+                     const void* output) {
+  const size_t es = gloo_hip_dtype_size(dtype);
+  try {
+    (void)gloo_amd::makeAlltoallPlan(GLOO_HIP_ALGO_ALLTOALL, rank, size, count, 1, lists);
+  } catch (const std::invalid_argument& e) {
+    GLOO_AMD_ENFORCE(false, e.what());
+  }
+  size_t in = 0, out = 0;  // elements this rank sends (its own block included) and receives
+  for (int q = 0; q < size; q++) {
+    in += lists.empty() ? count : (size_t)lists[q];
+    out += lists.empty() ? count : (size_t)lists[size + q];
+  }
+  GLOO_AMD_ENFORCE(input || in == 0, "alltoall: null input with ", in, " elements to send");         // alltoallv.cc:118
+  GLOO_AMD_ENFORCE(output || out == 0, "alltoall: null output with ", out, " elements to receive");  // alltoallv.cc:119
+  const char* a = static_cast<const char*>(input);
+  const char* b = static_cast<const char*>(output);
+  GLOO_AMD_ENFORCE(in == 0 || out == 0 || a + in * es <= b || b + out * es <= a, "alltoall: input [", input, ", +",
+                   in * es, ") and output [", output, ", +", out * es, ") overlap (there is no in-place form)");
+}
+
+bool allZero(const std::vector<int>& v) {
+  for (int x : v)
+    if (x != 0) return false;
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -207,6 +251,7 @@ int gloo_hip_algorithm_create_ws(gloo_hip_context_t ctx, int algo, int op, int d
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
+    refuseAlltoall(algo);
     std::vector<int> re;
     if (algo == GLOO_HIP_ALGO_REDUCE_SCATTER) {
       GLOO_AMD_ENFORCE(recv_elems, "reduce-scatter needs recv_elems");
@@ -238,6 +283,7 @@ int gloo_hip_algorithm_create_streams(gloo_hip_context_t ctx, int algo, int op, 
     if (const int rc = gloo_amd::checkBitwiseDtype(op, dtype)) return rc;  // before any exchange, as create_ws
   return guarded([&] {
     GLOO_AMD_ENFORCE(ctx && out && ptrs && nptrs >= 1, "bad arguments");
+    refuseAlltoall(algo);
     // gloo/cuda_allreduce_ring_chunked.cc:55-58
     // a gather / a scatter: a rank's pointer count differs between the root and
     // the others, and so would the stream lists; every rank passes one stream
@@ -494,6 +540,108 @@ int gloo_hip_scatter(gloo_hip_context_t ctx, const gloo_hip_scatter_options_t* o
     }
     runCached(ctx, GLOO_HIP_ALGO_SCATTER, GLOO_HIP_SUM, o->dtype, ins, {o->output}, o->elements, 0, o->tag, o->stream,
               {o->root});
+  });
+}
+
+int gloo_hip_alltoall_create(gloo_hip_context_t ctx, int dtype, void* input, void* output, size_t count,
+                             const int* matrix, gloo_hip_stream_t stream, int workspace, gloo_hip_algorithm_t* out) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && out, "null argument");
+    GLOO_AMD_ENFORCE(gloo_hip_dtype_size(dtype) > 0, "unknown dtype ", dtype);
+    const int P = ctx->ctx->size, me = ctx->ctx->rank;
+    std::vector<int> m;
+    if (matrix) {
+      m.assign(matrix, matrix + (size_t)P * P);
+      // the whole matrix, not only this rank's row and column: every rank derives every peer's plan from it
+      for (size_t k = 0; k < m.size(); k++)
+        GLOO_AMD_ENFORCE(m[k] >= 0, "alltoall: negative count ", m[k], " from rank ", k / P, " to rank ", k % P);
+      count = 0;  // ignored with a matrix, and part of the call's hash
+    }
+    alltoallBuffers(me, P, dtype, count, gloo_amd::alltoallLists(me, P, m), input, output);
+    auto a = std::make_unique<gloo_hip_algorithm>();
+    a->exec = gloo_amd::PlanExecutor::create(ctx->ctx, GLOO_HIP_ALGO_ALLTOALL, GLOO_HIP_SUM, dtype,
+                                             std::vector<void*>{output}, count, m, static_cast<hipStream_t>(stream),
+                                             std::vector<void*>{input}, 0, workspace);
+    *out = a.release();
+  });
+}
+
+int gloo_hip_alltoall(gloo_hip_context_t ctx, const gloo_hip_alltoall_options_t* o) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && o, "null argument");
+    const size_t es = gloo_hip_dtype_size(o->dtype);
+    GLOO_AMD_ENFORCE(es > 0, "unknown dtype ", o->dtype);
+    const int P = ctx->ctx->size, me = ctx->ctx->rank;
+    GLOO_AMD_ENFORCE(!o->in_counts == !o->out_counts, "alltoall: ", o->in_counts ? "in_counts" : "out_counts",
+                     " is given without ", o->in_counts ? "out_counts" : "in_counts", " (both, or neither)");
+    const bool lists = o->in_counts != nullptr;
+    // every refusal a rank can make from its own arguments comes first: before
+    // the count exchange of the own-lists form and before any construction
+    std::vector<int> m;  // the P x P matrix, once known
+    if (o->matrix) {
+      for (size_t k = 0; k < (size_t)P * P; k++) {
+        GLOO_AMD_ENFORCE(o->matrix[k] <= (size_t)INT32_MAX, "alltoall: count ", o->matrix[k], " from rank ", k / P,
+                         " to rank ", k % P, " is too large");
+        m.push_back((int)o->matrix[k]);
+      }
+    }
+    std::vector<int> mine;  // in_counts then out_counts
+    if (lists) {
+      for (int k = 0; k < 2 * P; k++) {
+        const size_t c = k < P ? o->in_counts[k] : o->out_counts[k - P];
+        GLOO_AMD_ENFORCE(c <= (size_t)INT32_MAX, "alltoall: ", k < P ? "in" : "out", "_count ", c, " for rank ", k % P,
+                         " is too large");
+        mine.push_back((int)c);
+      }
+      GLOO_AMD_ENFORCE(mine[me] == mine[P + me], "alltoall: rank ", me, "'s own block has in_count ", mine[me],
+                       " but out_count ", mine[P + me]);  // alltoallv.cc:138
+      if (o->matrix) {
+        const std::vector<int> want = gloo_amd::alltoallLists(me, P, m);
+        for (int k = 0; k < 2 * P; k++)
+          GLOO_AMD_ENFORCE(mine[k] == want[k], "alltoall: ", k < P ? "in" : "out", "_counts[", k % P, "] is ", mine[k],
+                           " but the matrix has ", want[k], k < P ? " from rank " : " to rank ", me,
+                           k < P ? " to rank " : " from rank ", k % P);
+      }
+    }
+    if (!lists && !o->matrix)
+      GLOO_AMD_ENFORCE(o->elements <= SIZE_MAX / es / (size_t)P, "alltoall: ", o->elements,
+                       " elements per block is too large");
+    // the buffers, against what this rank knows of the call so far
+    alltoallBuffers(me, P, o->dtype, o->elements, lists ? mine : gloo_amd::alltoallLists(me, P, m), o->input, o->output);
+    if (lists && !o->matrix) {
+      // The reference's alltoallv shape: a rank knows its own lists only.  The
+      // cached schedule's construction is collective, so every rank must hit
+      // and miss the cache alike, and a key made of a rank's own lists would
+      // not do that (a change between ranks 0 and 1 leaves the others' lists
+      // as they were).  So EVERY such call exchanges the lists once (the
+      // context's exchange counter advances alike on every rank), every rank
+      // assembles the same matrix and checks every pair from the same records,
+      // and the call goes on as the matrix form, whose key is the whole matrix.
+      std::vector<char> blob(mine.size() * sizeof(int));
+      std::memcpy(blob.data(), mine.data(), blob.size());
+      const auto all = ctx->ctx->allgather("alltoall/counts", blob);
+      m.assign((size_t)P * P, 0);
+      std::vector<int> outOf((size_t)P * P, 0);  // outOf[r * P + q]: what rank r expects from rank q
+      for (int q = 0; q < P; q++) {
+        GLOO_AMD_ENFORCE(all.at(q).size() == blob.size(), "alltoall: rank ", q, " exchanged ", all[q].size() / sizeof(int),
+                         " counts, not ", 2 * P, " (every rank must call the same form)");
+        std::vector<int> theirs(2 * (size_t)P);
+        std::memcpy(theirs.data(), all[q].data(), blob.size());
+        for (int r = 0; r < P; r++) {
+          m[(size_t)q * P + r] = theirs[r];
+          outOf[(size_t)q * P + r] = theirs[P + r];
+        }
+      }
+      for (int q = 0; q < P; q++)
+        for (int r = 0; r < P; r++)
+          GLOO_AMD_ENFORCE(m[(size_t)q * P + r] == outOf[(size_t)r * P + q], "alltoall: rank ", q, " sends ",
+                           m[(size_t)q * P + r], " elements to rank ", r, " (its in_counts[", r, "]) but rank ", r,
+                           " expects ", outOf[(size_t)r * P + q], " from rank ", q, " (its out_counts[", q, "])");
+    }
+    // nothing to move anywhere: every rank sees that from the same values
+    if (m.empty() ? o->elements == 0 : allZero(m)) return;
+    runCached(ctx, GLOO_HIP_ALGO_ALLTOALL, GLOO_HIP_SUM, o->dtype, {o->input}, {o->output}, m.empty() ? o->elements : 0,
+              0, o->tag, o->stream, m);
   });
 }
 

@@ -266,6 +266,10 @@ namespace {
 Plan planFor(int algo, int rank, int size, size_t count, int nin, int nout, size_t es, size_t maxSeg,
              const std::vector<int>& recvElems) {
   if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, nin, recvElems);  // {counts}, or none
+  // recvElems: none (even), or the size x size count matrix, the same on every
+  // rank; `rank`'s lists are its row and its column (plan.h alltoallLists).
+  // One input on every rank, whatever nin says of a peer.
+  if (isAlltoall(algo)) return makeAlltoallPlan(algo, rank, size, count, 1, alltoallLists(rank, size, recvElems));
   if (isNewStyle(algo)) {
     NewStyleOptions o;
     o.ninputs = nin;
@@ -514,6 +518,8 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     GLOO_AMD_ENFORCE(custom_ || isBuiltinOp(op_, dtype_), "unknown op ", op_, " for dtype ", dtype_);
   }
   GLOO_AMD_ENFORCE(!ptrs_.empty(), "need at least one pointer");
+  GLOO_AMD_ENFORCE(!isAlltoall(algo_) || (inputs_.size() == 1 && ptrs_.size() == 1),
+                   "alltoall has one input and one output, not ", inputs_.size(), " and ", ptrs_.size());
   for (void* p : ptrs_) GLOO_AMD_ENFORCE(p != nullptr || count_ == 0, "null device pointer");
   const int me = ctx_->rank, P = ctx_->size;
   // The executed plan: the algorithm's, or its mesh / pipelined form

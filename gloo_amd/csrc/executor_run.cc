@@ -605,7 +605,8 @@ void PlanExecutor::buildInterp() {
   // a gather's or a scatter's inputs on another GPU of the process keep the
   // enqueued plan, whose copies reach them directly (they are not staged:
   // their sizes are per block, not count_)
-  if (isRooted(planAlgo_) && anyRemote_) return fail();
+  // (an alltoall's likewise: its buffers are P blocks, not count_ elements)
+  if ((isRooted(planAlgo_) || isAlltoall(planAlgo_)) && anyRemote_) return fail();
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
     const size_t bytes = s.length * es_;
@@ -893,8 +894,88 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
                                     kCopyStorePlain),
               what);
   };
+  // The alltoall (plan.cc planAlltoall) with device signalling is the two
+  // rooted shapes back to back, on every rank.  Every pass is a set of
+  // independent (src -> dst) ranges and no source byte is read twice, so the
+  // multi-copy launch moves them and no kernel is added.  Sender side, the
+  // scatter root's shape: ONE wait for every peer's previous-run credit, then
+  // the SENDs (flagged, one channel and ticket counter each) and the own block
+  // (no flag, plain stores) as entries of launchCopySignalMulti,
+  // kMaxCopyEntries a launch.  Receiver side, the gather root's: ONE wait for
+  // every arrival, the copy-outs as flag-less entries, the credits in one
+  // launchSignalMulti.  Empty blocks have no step and so no entry.  Event
+  // profiling and buffers on other GPUs of the process keep the plan's own
+  // steps.  (Input and output share no byte, include/gloo_amd.h; an own block
+  // whose two ranges meet all the same keeps the plan's COPY step.)
+  const bool alltoall = isAlltoall(planAlgo_) && deviceSignal_ && !profiling_ && !anyRemote_;
+  auto ownBlockJoins = [&](const Step& c) {
+    const size_t bytes = c.length * es_;
+    return c.kind == GLOO_HIP_STEP_COPY && (c.flags & GLOO_HIP_FROM_INPUTS) && bytes > 0 &&
+           disjoint(userPtr(0) + c.dst_off * es_, bytes, copySrc(c), bytes);
+  };
   for (size_t i = 0; i < steps.size(); i++) {
     const Step& s = steps[i];
+    if (alltoall && (s.kind == GLOO_HIP_STEP_WAIT_NOTIFY ||
+                     (ownBlockJoins(s) && i + 1 < steps.size() && steps[i + 1].kind == GLOO_HIP_STEP_WAIT_NOTIFY))) {
+      const bool own = s.kind == GLOO_HIP_STEP_COPY;
+      size_t j = own ? i + 1 : i;
+      std::vector<const uint64_t*> flags;
+      std::vector<Seq> targets;
+      std::vector<CopyDesc> d;
+      while (j + 1 < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_NOTIFY && steps[j + 1].kind == GLOO_HIP_STEP_SEND &&
+             steps[j + 1].peer == steps[j].peer && (steps[j + 1].flags & GLOO_HIP_FROM_INPUTS) && steps[j + 1].length > 0) {
+        const Step& t = steps[j + 1];
+        const size_t bytes = t.length * es_;
+        flags.push_back(waitFlag(steps[j].peer, steps[j].slot));
+        targets.push_back(seqOf(j, r, graph));
+        d.push_back(CopyDesc{sendDst(t), sendSrc(t), bytes, sigFlag(t.peer, t.slot), seqOf(j + 1, r, graph),
+                             ticket_ + (size_t)t.peer * GLOO_HIP_NUM_SLOTS + t.slot,
+                             copySignalGrid(bytes, copyBlocksFor(t.peer))});
+        j += 2;
+      }
+      if (!d.empty()) {
+        if (own) {
+          const size_t bytes = s.length * es_;
+          d.push_back(CopyDesc{userPtr(0) + s.dst_off * es_, copySrc(s), bytes, nullptr, Seq{}, nullptr,
+                               copySignalGrid(bytes, kCopyOutBlocks)});
+        }
+        GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                           ctx_->errorWordDevicePtr(me), stream_));
+        localCopies(d, "copy_signal_kernel (alltoall sends)");
+        i = j - 1;
+        continue;
+      }
+    }
+    if (alltoall && s.kind == GLOO_HIP_STEP_WAIT_RECV) {
+      size_t j = i;
+      std::vector<const uint64_t*> flags;
+      std::vector<Seq> targets;
+      for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_WAIT_RECV; j++) {
+        flags.push_back(waitFlag(steps[j].peer, steps[j].slot));
+        targets.push_back(seqOf(j, r, graph));
+      }
+      std::vector<CopyDesc> d;
+      for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_COPY && steps[j].flags == GLOO_HIP_SRC_ARENA; j++) {
+        const Step& t = steps[j];
+        const size_t bytes = t.length * es_;
+        if (bytes)
+          d.push_back(CopyDesc{userPtr(0) + t.dst_off * es_, arenaAt(t.src_off, t.length), bytes, nullptr, Seq{}, nullptr,
+                               copySignalGrid(bytes, kCopyOutBlocks)});
+      }
+      std::vector<uint64_t*> credits;
+      std::vector<Seq> values;
+      for (; j < steps.size() && steps[j].kind == GLOO_HIP_STEP_NOTIFY; j++) {
+        credits.push_back(sigFlag(steps[j].peer, steps[j].slot));
+        values.push_back(seqOf(j, r, graph));
+      }
+      GLOO_AMD_HIP_CHECK(launchWaitMulti(flags.data(), targets.data(), (int)flags.size(), epoch, timeoutTicks,
+                                         ctx_->errorWordDevicePtr(me), stream_));
+      localCopies(d, "copy kernel (alltoall copy-outs)");
+      if (!credits.empty())
+        GLOO_AMD_HIP_CHECK(launchSignalMulti(credits.data(), values.data(), (int)credits.size(), epoch, stream_));
+      i = j - 1;
+      continue;
+    }
     if (rooted && isScatter(planAlgo_) && s.kind == GLOO_HIP_STEP_WAIT_NOTIFY) {
       size_t j = i;
       std::vector<const uint64_t*> flags;

@@ -1321,9 +1321,9 @@ Plan planAllgather(int rank, int size, uint64_t count, int ninputs, const std::v
 // inbox, awaited by the sender's NEXT run (WAIT_NOTIFY | GLOO_HIP_PREV_RUN).
 // Arena: laid out like the output; peer q's inbox is arena[outOff[q],
 // +out_counts[q]).  Empty blocks are skipped on both sides, both knowing the
-// counts (that in_counts_q[r] == out_counts_r[q] for every pair is for an
-// executor's construction to check before any byte moves; none runs this plan
-// yet).
+// counts.  The executor describes the call by the whole P x P matrix and feeds
+// this planner row `rank` and column `rank` of it (alltoallLists below), so
+// in_counts_q[r] == out_counts_r[q] holds for every pair before any byte moves.
 // ---------------------------------------------------------------------------
 Plan planAlltoall(int rank, int size, uint64_t count, const std::vector<int>& counts) {
   if (!counts.empty() && (int)counts.size() != 2 * size)
@@ -1487,6 +1487,20 @@ Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs,
   return planAlltoall(rank, size, count, counts);
 }
 
+std::vector<int> alltoallLists(int rank, int size, const std::vector<int>& matrix) {
+  if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
+  if (matrix.empty()) return {};
+  if (matrix.size() != (size_t)size * (size_t)size)
+    throw std::invalid_argument("alltoall: a count matrix of " + std::to_string(matrix.size()) + " entries for " +
+                                std::to_string(size) + " ranks (" + std::to_string((size_t)size * size) + " expected)");
+  std::vector<int> lists(2 * (size_t)size);
+  for (int q = 0; q < size; q++) {
+    lists[q] = matrix[(size_t)rank * size + q];         // row: what this rank sends to q
+    lists[size + q] = matrix[(size_t)q * size + rank];  // column: what q sends to this rank
+  }
+  return lists;
+}
+
 Plan makeAllgatherPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts) {
   if (size < 1 || rank < 0 || rank >= size) throw std::invalid_argument("bad rank/size");
   // every block goes to every rank in one hop already: there is nothing to derive
@@ -1520,8 +1534,9 @@ Plan makePlan(int algo, int rank, int size, uint64_t count, int nptrs, const std
   if (isAllgather(algo)) return makeAllgatherPlan(algo, rank, size, count, 0, recvElems);  // in place
   if (isGather(algo)) return makeGatherPlan(algo, rank, size, count, recvElems);
   if (isScatter(algo)) return makeScatterPlan(algo, rank, size, count, recvElems);
-  // (GLOO_HIP_ALGO_ALLTOALL is a planner only so far: gloo_hip_plan / gloo_hip_plan_ex build it, no
-  // executor runs it, and it falls through to "unknown algorithm" here)
+  // (GLOO_HIP_ALGO_ALLTOALL has two pointer roles and a count matrix, which this signature does not carry:
+  // gloo_hip_plan_ex and the executor build it through makeAlltoallPlan, and it falls through to "unknown
+  // algorithm" here)
   if (algo & GLOO_HIP_ALGO_MESH) {
     const int base = algo & ~GLOO_HIP_ALGO_MESH;
     // an order of the reference's own route: a mesh plan has no first send
@@ -1646,6 +1661,27 @@ extern "C" int gloo_hip_plan_ex(int algo, int rank, int size, size_t count, int 
       if (capacity < p.steps.size()) return GLOO_HIP_EINVAL_ARG;
       if (!p.steps.empty()) std::memcpy(steps, p.steps.data(), p.steps.size() * sizeof(gloo_hip_step_t));
     }
+    return GLOO_HIP_OK;
+  } catch (const std::exception& e) {
+    if (gloo_amd::planErrorSink) gloo_amd::planErrorSink(GLOO_HIP_EINVAL_ARG, e.what());
+    return GLOO_HIP_EINVAL_ARG;
+  }
+}
+
+// Row `rank` then column `rank` of a size x size alltoall count matrix: the
+// 2 * size entries gloo_hip_plan_ex takes as recv_elems for that rank
+// (gloo_amd::alltoallLists; the executor derives every rank's plan this way).
+extern "C" int gloo_hip_alltoall_lists(int rank, int size, const int* matrix, int* lists) {
+  try {
+    if (!matrix || !lists) throw std::invalid_argument("gloo_hip_alltoall_lists: null matrix or lists");
+    if (size < 1 || size > 46340)  // size * size entries, counted in an int by callers
+      throw std::invalid_argument("gloo_hip_alltoall_lists: size " + std::to_string(size) + " out of range");
+    if (rank < 0 || rank >= size)
+      throw std::invalid_argument("gloo_hip_alltoall_lists: rank " + std::to_string(rank) + " outside [0, " +
+                                  std::to_string(size) + ")");
+    const std::vector<int> m(matrix, matrix + (size_t)size * size);
+    const std::vector<int> l = gloo_amd::alltoallLists(rank, size, m);
+    std::memcpy(lists, l.data(), l.size() * sizeof(int));
     return GLOO_HIP_OK;
   } catch (const std::exception& e) {
     if (gloo_amd::planErrorSink) gloo_amd::planErrorSink(GLOO_HIP_EINVAL_ARG, e.what());

@@ -27,6 +27,13 @@
 //        gloo/scatter.cc:19-61)     ->  gloo::hip::scatter(opts[, stream])
 //        (bytes only; the reference's own route, every block one hop to or
 //        from the root)
+//   gloo::alltoall(gloo::AlltoallOptions&)           (gloo/alltoall.h,
+//        gloo/alltoall.cc:19-72)    ->  gloo::hip::alltoall(opts[, stream])
+//   gloo::alltoallv(gloo::AlltoallvOptions&)         (gloo/alltoallv.h,
+//        gloo/alltoallv.cc:117-170) ->  gloo::hip::alltoallv(opts[, stream])
+//        (bytes only; the reference's own route, every block one hop; input
+//        and output may share no byte; alltoallv costs one host exchange of
+//        the counts per call, include/gloo_amd.h)
 //
 // The caller fills the SAME option object it would hand to gloo::allreduce /
 // gloo::reduce: setInput(s) / setOutput(s) with DEVICE pointers (the
@@ -65,6 +72,8 @@
 #include "gloo/allgather.h"
 #include "gloo/allgatherv.h"
 #include "gloo/allreduce.h"
+#include "gloo/alltoall.h"
+#include "gloo/alltoallv.h"
 #include "gloo/broadcast.h"
 #include "gloo/gather.h"
 #include "gloo/gatherv.h"
@@ -287,6 +296,41 @@ struct ScatterAccess : ::gloo::ScatterOptions {
   static size_t get_elementSize(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::elementSize); }
   static int get_root(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::root); }
   static uint32_t get_tag(const ::gloo::ScatterOptions& o) { return o.*(&ScatterAccess::tag); }
+};
+
+struct AlltoallAccess : ::gloo::AlltoallOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::AlltoallOptions& o) {
+    return o.*(&AlltoallAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::AlltoallOptions& o) {
+    return o.*(&AlltoallAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::AlltoallOptions& o) {
+    return o.*(&AlltoallAccess::out);
+  }
+  static size_t get_elementSize(const ::gloo::AlltoallOptions& o) { return o.*(&AlltoallAccess::elementSize); }
+  static uint32_t get_tag(const ::gloo::AlltoallOptions& o) { return o.*(&AlltoallAccess::tag); }
+};
+
+struct AlltoallvAccess : ::gloo::AlltoallvOptions {
+  static const std::shared_ptr<::gloo::Context>& get_context(const ::gloo::AlltoallvOptions& o) {
+    return o.*(&AlltoallvAccess::context);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_in(const ::gloo::AlltoallvOptions& o) {
+    return o.*(&AlltoallvAccess::in);
+  }
+  static const std::unique_ptr<::gloo::transport::UnboundBuffer>& get_out(const ::gloo::AlltoallvOptions& o) {
+    return o.*(&AlltoallvAccess::out);
+  }
+  // byte lengths per rank (alltoallv.cc:19-31 splitOffsetsAndLengths); the offsets are their prefix sums
+  static const std::vector<size_t>& get_inLengths(const ::gloo::AlltoallvOptions& o) {
+    return o.*(&AlltoallvAccess::inLengthPerRank);
+  }
+  static const std::vector<size_t>& get_outLengths(const ::gloo::AlltoallvOptions& o) {
+    return o.*(&AlltoallvAccess::outLengthPerRank);
+  }
+  static size_t get_elementSize(const ::gloo::AlltoallvOptions& o) { return o.*(&AlltoallvAccess::elementSize); }
+  static uint32_t get_tag(const ::gloo::AlltoallvOptions& o) { return o.*(&AlltoallvAccess::tag); }
 };
 
 }  // namespace detail
@@ -552,6 +596,63 @@ inline void scatter(::gloo::ScatterOptions& opts, hipStream_t stream = nullptr) 
   g.tag = A::get_tag(opts);
   g.stream = stream;
   ::gloo::hip_bridge::check(gloo_hip_scatter(ctx, &g), "gloo::hip::scatter");
+}
+
+// gloo::alltoall(opts) (gloo/alltoall.cc:19-72) on device buffers: block q of
+// rank r's output receives block r of rank q's input, every block in->size /
+// P bytes.  The options carry an element size and no type, and an alltoall
+// moves bytes, so the call goes down in uint8.  Input and output may share no
+// byte (the reference's memcpy of the own block asks the same).
+inline void alltoall(::gloo::AlltoallOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::AlltoallAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_elementSize(opts) > 0);            // gloo/alltoall.cc:26
+  GLOO_ENFORCE(A::get_in(opts), "no input buffer");      // :27
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");    // :28
+  const size_t bytes = A::get_in(opts)->size;
+  GLOO_ENFORCE(bytes % (size_t)ctxp->size == 0);         // :29
+  GLOO_ENFORCE(bytes == A::get_out(opts)->size);         // :30
+  if (bytes == 0) return;
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, A::get_out(opts)->ptr);
+  gloo_hip_alltoall_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.input = A::get_in(opts)->ptr;
+  g.output = A::get_out(opts)->ptr;
+  g.elements = bytes / (size_t)ctxp->size;
+  g.in_counts = g.out_counts = g.matrix = nullptr;
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_alltoall(ctx, &g), "gloo::hip::alltoall");
+}
+
+// gloo::alltoallv(opts) (gloo/alltoallv.cc:117-170): this rank sends
+// inLengthPerRank[q] bytes to rank q and receives outLengthPerRank[q] from it,
+// at the prefix offsets (:19-31).  A rank knows its own lists only, so every
+// call exchanges them once on the host and every rank checks every pair
+// (include/gloo_amd.h, the own-lists form of gloo_hip_alltoall).
+inline void alltoallv(::gloo::AlltoallvOptions& opts, hipStream_t stream = nullptr) {
+  using A = detail::AlltoallvAccess;
+  const auto& ctxp = A::get_context(opts);
+  GLOO_ENFORCE(A::get_elementSize(opts) > 0);            // gloo/alltoallv.cc:130
+  GLOO_ENFORCE(A::get_in(opts), "no input buffer");      // :131
+  GLOO_ENFORCE(A::get_out(opts), "no output buffer");    // :132
+  const std::vector<size_t>& in = A::get_inLengths(opts);
+  const std::vector<size_t>& out = A::get_outLengths(opts);
+  GLOO_ENFORCE_EQ(in.size(), (size_t)ctxp->size);        // :52
+  GLOO_ENFORCE_EQ(out.size(), (size_t)ctxp->size);       // :89
+  GLOO_ENFORCE(in[ctxp->rank] == out[ctxp->rank]);       // :138
+  gloo_hip_context_t ctx = detail::contextFor(ctxp, A::get_out(opts)->ptr);
+  gloo_hip_alltoall_options_t g;
+  g.dtype = GLOO_HIP_U8;
+  g.input = A::get_in(opts)->ptr;
+  g.output = A::get_out(opts)->ptr;
+  g.elements = 0;
+  g.in_counts = in.data();
+  g.out_counts = out.data();
+  g.matrix = nullptr;
+  g.tag = A::get_tag(opts);
+  g.stream = stream;
+  ::gloo::hip_bridge::check(gloo_hip_alltoall(ctx, &g), "gloo::hip::alltoallv");
 }
 
 // Collective: tears down the library context (and its cached schedules)

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -667,6 +668,148 @@ inline void scatter(const ScatterOptions& o) {
   PlanExecutor exec(o.context_, GLOO_HIP_ALGO_SCATTER, GLOO_HIP_SUM /* not used */, o.dtype_, {o.output_},
                     o.outputElements_, {o.root_}, o.stream_, root ? o.inputs_ : std::vector<void*>{});
   exec.run();
+}
+
+// gloo::AlltoallOptions (gloo/alltoall.h) over device pointers: one input and
+// one output of the same element count, a multiple of the ranks; block q of
+// the input goes to rank q.  Input and output may share no byte.
+class AlltoallOptions {
+ public:
+  explicit AlltoallOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInput(T* ptr, size_t elements) {
+    input_ = ptr;
+    inputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, size_t elements) {
+    output_ = ptr;
+    outputElements_ = elements;
+    dtype_ = DType<T>::value;
+  }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  void* input_ = nullptr;
+  void* output_ = nullptr;
+  size_t inputElements_ = 0, outputElements_ = 0;
+  int dtype_ = GLOO_HIP_U8;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+
+// gloo::AlltoallvOptions (gloo/alltoallv.h) over device pointers: this rank
+// sends inCounts[q] elements to rank q and receives outCounts[q] from it, at
+// the prefix offsets (alltoallv.cc:19-31).  setMatrix (optional): the whole
+// P x P matrix, [q * P + r] the elements from rank q to rank r, the same on
+// every rank; alltoallv then skips its host exchange of the counts.
+class AlltoallvOptions {
+ public:
+  explicit AlltoallvOptions(const std::shared_ptr<Context>& context) : context_(context) {}
+  template <typename T>
+  void setInput(T* ptr, std::vector<size_t> counts) {
+    input_ = ptr;
+    inCounts_ = std::move(counts);
+    dtype_ = DType<T>::value;
+  }
+  template <typename T>
+  void setOutput(T* ptr, std::vector<size_t> counts) {
+    output_ = ptr;
+    outCounts_ = std::move(counts);
+    dtype_ = DType<T>::value;
+  }
+  void setMatrix(std::vector<int> matrix) { matrix_ = std::move(matrix); }
+  void setTag(uint32_t tag) { tag_ = tag; }
+  void setStream(hipStream_t s) { stream_ = s; }
+
+  std::shared_ptr<Context> context_;
+  void* input_ = nullptr;
+  void* output_ = nullptr;
+  std::vector<size_t> inCounts_, outCounts_;
+  std::vector<int> matrix_;
+  int dtype_ = GLOO_HIP_U8;
+  uint32_t tag_ = 0;
+  hipStream_t stream_ = nullptr;
+};
+
+namespace detail {
+// `matrix` empty: the even form of `count` elements per block.  in / out: the
+// elements this rank sends and receives (for the buffers' overlap check).
+inline void runAlltoall(const std::shared_ptr<Context>& ctx, int dtype, void* input, void* output, size_t count,
+                        const std::vector<int>& matrix, size_t in, size_t out, hipStream_t stream) {
+  const size_t es = gloo_hip_dtype_size(dtype);
+  GLOO_AMD_ENFORCE(es > 0, "alltoall: unknown dtype ", dtype);
+  const char* a = static_cast<const char*>(input);
+  const char* b = static_cast<const char*>(output);
+  GLOO_AMD_ENFORCE(in == 0 || out == 0 || a + in * es <= b || b + out * es <= a,
+                   "alltoall: input and output overlap (there is no in-place form)");
+  PlanExecutor exec(ctx, GLOO_HIP_ALGO_ALLTOALL, GLOO_HIP_SUM /* not used */, dtype, {output}, count, matrix, stream,
+                    {input});
+  exec.run();
+}
+}  // namespace detail
+
+// gloo::alltoall(opts) (gloo/alltoall.cc:19-72).
+inline void alltoall(const AlltoallOptions& o) {
+  const size_t P = (size_t)o.context_->size;
+  GLOO_AMD_ENFORCE(o.inputElements_ % P == 0, "alltoall: an input of ", o.inputElements_, " elements for ", P,
+                   " ranks");  // .cc:29
+  GLOO_AMD_ENFORCE(o.inputElements_ == o.outputElements_, "alltoall: an input of ", o.inputElements_,
+                   " elements, an output of ", o.outputElements_);  // .cc:30
+  if (o.inputElements_ == 0) return;
+  GLOO_AMD_ENFORCE(o.input_ && o.output_, "alltoall: no input or no output");  // .cc:27-28
+  detail::runAlltoall(o.context_, o.dtype_, o.input_, o.output_, o.inputElements_ / P, {}, o.inputElements_,
+                      o.outputElements_, o.stream_);
+}
+
+// gloo::alltoallv(opts) (gloo/alltoallv.cc:117-170).  Without setMatrix the
+// ranks exchange their lists once on the host (every call), every rank
+// assembles the matrix from the same records and checks every pair, so a
+// mismatch raises on every rank alike before any byte moves.
+inline void alltoallv(const AlltoallvOptions& o) {
+  const int P = o.context_->size, me = o.context_->rank;
+  GLOO_AMD_ENFORCE((int)o.inCounts_.size() == P, "alltoallv: ", o.inCounts_.size(), " in_counts for ", P, " ranks");  // .cc:52
+  GLOO_AMD_ENFORCE((int)o.outCounts_.size() == P, "alltoallv: ", o.outCounts_.size(), " out_counts for ", P,
+                   " ranks");  // .cc:89
+  std::vector<int> mine;
+  size_t in = 0, out = 0;
+  for (int k = 0; k < 2 * P; k++) {
+    const size_t c = k < P ? o.inCounts_[k] : o.outCounts_[k - P];
+    GLOO_AMD_ENFORCE(c <= (size_t)INT32_MAX, "alltoallv: count ", c, " is too large");
+    mine.push_back((int)c);
+    (k < P ? in : out) += c;
+  }
+  GLOO_AMD_ENFORCE(mine[me] == mine[P + me], "alltoallv: rank ", me, "'s own block has in_count ", mine[me],
+                   " but out_count ", mine[P + me]);  // .cc:138
+  GLOO_AMD_ENFORCE(o.input_ || in == 0, "alltoallv: no input");    // .cc:131
+  GLOO_AMD_ENFORCE(o.output_ || out == 0, "alltoallv: no output");  // .cc:132
+  std::vector<int> m = o.matrix_;
+  if (m.empty()) {
+    std::vector<char> blob(mine.size() * sizeof(int));
+    std::memcpy(blob.data(), mine.data(), blob.size());
+    const auto all = o.context_->allgather("alltoall/counts", blob);
+    m.assign((size_t)P * P, 0);
+    std::vector<int> expect((size_t)P * P, 0);  // [r * P + q]: what rank r expects from rank q
+    for (int q = 0; q < P; q++) {
+      GLOO_AMD_ENFORCE(all.at(q).size() == blob.size(), "alltoallv: bad count record from rank ", q);
+      std::memcpy(&m[(size_t)q * P], all[q].data(), P * sizeof(int));
+      std::memcpy(&expect[(size_t)q * P], all[q].data() + P * sizeof(int), P * sizeof(int));
+    }
+    for (int q = 0; q < P; q++)
+      for (int r = 0; r < P; r++)
+        GLOO_AMD_ENFORCE(m[(size_t)q * P + r] == expect[(size_t)r * P + q], "alltoallv: rank ", q, " sends ",
+                         m[(size_t)q * P + r], " elements to rank ", r, " but rank ", r, " expects ",
+                         expect[(size_t)r * P + q], " from rank ", q);
+  } else {
+    const std::vector<int> want = alltoallLists(me, P, m);
+    GLOO_AMD_ENFORCE(want == mine, "alltoallv: the matrix's row and column ", me, " differ from this rank's counts");
+  }
+  bool any = false;
+  for (int v : m) any = any || v != 0;
+  if (!any) return;
+  detail::runAlltoall(o.context_, o.dtype_, o.input_, o.output_, 0, m, in, out, o.stream_);
 }
 
 }  // namespace gloo_amd

@@ -43,6 +43,14 @@ inline bool isAllgather(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_
 // != out_counts[rank] are refused.
 Plan makeAlltoallPlan(int algo, int rank, int size, uint64_t count, int ninputs, const std::vector<int>& counts);
 inline bool isAlltoall(int algo) { return (algo & ~GLOO_HIP_ALGO_MESH) == GLOO_HIP_ALGO_ALLTOALL; }
+// The executor's description of an alltoall is the same on every rank: no
+// list (the even form), or the size x size matrix M with M[q * size + r] the
+// elements rank q sends to rank r.  Rank r's lists for makeAlltoallPlan are
+// row r (its in_counts) then column r (its out_counts), so in_counts_q[r] ==
+// out_counts_r[q] holds for every pair by construction and every rank derives
+// every peer's plan.  An empty matrix gives an empty list; any other length
+// than size * size is refused.
+std::vector<int> alltoallLists(int rank, int size, const std::vector<int>& matrix);
 // GLOO_HIP_ALGO_GATHER (plan.cc planGather): one input per rank, one output
 // on the root.  recvElems = {root}: every block `count` elements; {root, c_0
 // ... c_{size-1}}: gatherv, `count` ignored.  Any other length, a root outside

@@ -373,14 +373,18 @@ typedef enum {
    * this plan; with device signalling the LOCAL_GATHER and every SEND are ONE
    * pass that reads each input tile once (reduce.hip gather_fanout_kernel). */
   GLOO_HIP_ALGO_ALLGATHER = 13,
-  /* gloo::alltoall and gloo::alltoallv (gloo/alltoall.cc, gloo/alltoallv.cc):
-   * A PLAN ONLY so far: gloo_hip_plan / gloo_hip_plan_ex build it; no executor
-   * runs it, and gloo_hip_algorithm_create* refuse the code as an unknown
-   * algorithm.  ONE input and ONE output per rank, separate buffers.  Rank r's
+  /* gloo::alltoall and gloo::alltoallv (gloo/alltoall.cc, gloo/alltoallv.cc).
+   * Run through gloo_hip_alltoall_create (the algorithm object) and
+   * gloo_hip_alltoall (function style), both below; gloo_hip_algorithm_create*
+   * keep refusing the code as an unknown algorithm, because an alltoall's
+   * pointers ({input, output}, neither a list) and its P x P count matrix do
+   * not fit their signature.  ONE input and ONE output per rank, separate
+   * buffers that share no byte (there is no in-place form).  Rank r's
    * input is P blocks back to back, block q (in_counts[q] elements) for rank
    * q; its output is P blocks back to back, block q (out_counts[q] elements)
    * from rank q; offsets are the prefix sums (alltoallv.cc:19-31):
    *   out_r[outOff_r[q], +out_counts_r[q]) == in_q[inOff_q[r], +in_counts_q[r])
+   * Not a reduction: there is no op, dtype gives the element size.
    * gloo_hip_plan_ex(14, rank, size, count, ninputs = 1, noutputs = 1, ...,
    * recv_elems): recv_elems NULL is the even form, `count` elements per block
    * (alltoall.cc:29-30); otherwise it has 2 * size entries, in_counts[0..size)
@@ -399,9 +403,19 @@ typedef enum {
    * copied LAST run's block out of its inbox), then SEND |
    * GLOO_HIP_FROM_INPUTS of input block q; for each peer rank-1, rank-2, ...:
    * WAIT_RECV; one COPY arena -> output per peer; one NOTIFY (the credit)
-   * per peer; WAIT_SEND per peer sent to.  One rank: the COPY alone.  A
-   * sender writes one-sidedly, so an executor of this plan has to check
-   * in_counts_q[r] == out_counts_r[q] for every pair before a byte moves. */
+   * per peer; WAIT_SEND per peer sent to.  One rank: the COPY alone.  A total
+   * of 0: no steps.  The credit orders run r + 1's send after run r's copy out
+   * of the inbox, so runs need no barrier.  The executor never promotes this
+   * plan.
+   * A sender writes one-sidedly, so in_counts_q[r] == out_counts_r[q] must
+   * hold for every pair before a byte moves.  The executor gets it by
+   * construction: it describes the call by the whole P x P matrix M (M[q * P +
+   * r]: elements from rank q to rank r), the same on every rank, and plans
+   * rank r from row r and column r (gloo_hip_alltoall_lists).  A rank that
+   * passed another matrix is refused on every rank at construction.  With
+   * device signalling a run is two multi-copy launches between two multi-flag
+   * waits (the sends and the own block; the copy-outs), and one launch of
+   * credits; no kernel is specific to it. */
   GLOO_HIP_ALGO_ALLTOALL = 14,
   /* gloo::gather and gloo::gatherv (gloo/gather.cc, gloo/gatherv.cc): every
    * rank contributes ONE input of counts[rank] elements; afterwards the
@@ -523,7 +537,7 @@ typedef enum {
  * output 0 (new-style allreduce; one input = copy), instead of folding the
  * outputs into output 0.  On REDUCE: user[dst] = input0[dst] op arena[src]
  * (gloo::reduce's out = in op tmp); on SEND: the source is input 0; on COPY
- * (GLOO_HIP_ALGO_ALLTOALL's own block, a plan no executor runs yet): the
+ * (the own block of GLOO_HIP_ALGO_ALLTOALL and of the rooted collectives): the
  * source is input 0 as well, user[dst_off, +length) = input0[src_off, +length).
  * WHICH input a SEND or a COPY reads is in bits 8 and up of `flags`:
  * GLOO_HIP_INPUT(q) names input q, GLOO_HIP_INPUT_OF(flags) reads it back.
@@ -768,7 +782,8 @@ int gloo_hip_algorithm_stats(gloo_hip_algorithm_t algo, double* stats4);
 int gloo_hip_algorithm_mode(gloo_hip_algorithm_t algo, int* mode4);
 /* The same for the schedule that ran the latest function-style call
  * (gloo_hip_allreduce / gloo_hip_reduce_to_root / gloo_hip_broadcast /
- * gloo_hip_allgather / gloo_hip_gather / gloo_hip_scatter) on `ctx`. */
+ * gloo_hip_allgather / gloo_hip_gather / gloo_hip_scatter / gloo_hip_alltoall)
+ * on `ctx`. */
 int gloo_hip_context_mode(gloo_hip_context_t ctx, int* mode4);
 
 /* ------------------------------------------------------------------------
@@ -920,6 +935,77 @@ typedef struct {
 } gloo_hip_scatter_options_t;
 
 int gloo_hip_scatter(gloo_hip_context_t ctx, const gloo_hip_scatter_options_t* opts);
+
+/* ------------------------------------------------------------------------
+ * gloo::alltoall(AlltoallOptions&) (gloo/alltoall.h, gloo/alltoall.cc) and
+ * gloo::alltoallv(AlltoallvOptions&) (gloo/alltoallv.h, gloo/alltoallv.cc):
+ * GLOO_HIP_ALGO_ALLTOALL above.  Afterwards block q of rank r's `output` holds
+ * block r of rank q's `input`.
+ *
+ * gloo_hip_alltoall_create is the algorithm object (create once,
+ * gloo_hip_algorithm_run many times, gloo_hip_algorithm_destroy; the stats,
+ * mode and profiling calls apply).  matrix NULL: the even form, `count`
+ * elements per block.  Otherwise matrix has size * size ints, matrix[q * size
+ * + r] the elements rank q sends to rank r, THE SAME ON EVERY RANK, and count
+ * is ignored; this rank's input is row `rank` back to back, its output column
+ * `rank`.  Collective.  One stream, or NULL for the algorithm's own (run()
+ * then returns with the output complete).  workspace: GLOO_HIP_WORKSPACE_*.
+ * Refused on this rank before any exchange, the last-error text naming the
+ * value: a bad dtype, a negative count anywhere in the matrix, a NULL input or
+ * output where this rank has elements to send or receive, an input that
+ * shares a byte with the output.  A rank that passed another matrix (or
+ * count, or dtype) than rank 0 makes the construction fail on EVERY rank,
+ * before a byte moves.
+ *
+ * gloo_hip_alltoall is the function-style call, cached per option set like
+ * gloo_hip_allgather; gloo_hip_context_mode reports the schedule that ran.
+ * Three forms:
+ *   even       in_counts, out_counts and matrix NULL: `elements` per block.
+ *              Cached per (dtype, elements, tag).
+ *   matrix     matrix given (size * size entries, the same on every rank; the
+ *              own lists may be given too and must then equal its row and
+ *              column `rank`).  Cached per (dtype, matrix, tag).  No count
+ *              exchange: ranks that disagree are refused at construction.
+ *   own lists  in_counts and out_counts only, `size` entries each: the
+ *              reference's alltoallv, where a rank knows its own blocks only.
+ *              EVERY call of this form costs one host exchange of the 2 * size
+ *              counts through the context's store: every rank assembles the
+ *              matrix from the same records and checks every pair, so a
+ *              mismatch is refused on every rank alike, naming the pair and
+ *              both values, before any schedule is built or any byte moves;
+ *              the call then goes on as the matrix form.  (The cache key must
+ *              be the same on every rank, because building a schedule is
+ *              collective; a rank's own lists are not.)  Callers with fixed
+ *              counts, and callers who can supply the matrix, should use the
+ *              other two forms.
+ * in_counts and out_counts are both given or both NULL.  Refused before any
+ * exchange, naming the value: a bad dtype, only one of the two lists, a count
+ * above INT32_MAX, in_counts[rank] != out_counts[rank] (alltoallv.cc:138), a
+ * matrix whose row or column `rank` differs from the own lists, a NULL input
+ * or output where there are elements to move, overlapping input and output.
+ * A total of 0 on every rank returns at once.
+ *
+ * gloo_hip_alltoall_lists writes row `rank` then column `rank` of `matrix`
+ * (size * size ints) to lists[0, 2 * size): the recv_elems gloo_hip_plan_ex
+ * takes for that rank, as the executor derives them.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int dtype;                /* gloo_hip_dtype_t                                      */
+  void* input;              /* device pointer: `size` blocks back to back            */
+  void* output;             /* device pointer: `size` blocks back to back            */
+  size_t elements;          /* per block; the even form only                         */
+  const size_t* in_counts;  /* NULL, or `size` entries: elements for each rank       */
+  const size_t* out_counts; /* NULL, or `size` entries: elements from each rank      */
+  const size_t* matrix;     /* NULL, or size * size entries, [q * size + r]: q to r  */
+  uint32_t tag;             /* setTag                                                */
+  gloo_hip_stream_t stream; /* NULL: the output is complete on return                */
+} gloo_hip_alltoall_options_t;
+
+int gloo_hip_alltoall(gloo_hip_context_t ctx, const gloo_hip_alltoall_options_t* opts);
+int gloo_hip_alltoall_create(gloo_hip_context_t ctx, int dtype, void* input, void* output, size_t count,
+                             const int* matrix /* NULL: even */, gloo_hip_stream_t stream, int workspace,
+                             gloo_hip_algorithm_t* out);
+int gloo_hip_alltoall_lists(int rank, int size, const int* matrix, int* lists);
 
 /* ------------------------------------------------------------------------
  * The xGMI transport: bound buffers of gloo::transport::Pair / Buffer
