@@ -393,6 +393,7 @@ def _bind_collectives(L):
     L.gloo_hip_algorithm_set_streams.argtypes = [vp, ctypes.POINTER(vp), ctypes.c_int]
     L.gloo_hip_ipc_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.gloo_hip_ipc_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
+    L.gloo_hip_context_agree_on_sharing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
     L.gloo_hip_algorithm_run.argtypes = [vp]
     L.gloo_hip_algorithm_destroy.argtypes = [vp]
     L.gloo_hip_algorithm_wait_seconds.argtypes = [vp]
@@ -410,7 +411,7 @@ EXPORTED = EXPORTED + ("gloo_hip_context_create", "gloo_hip_context_create_ex", 
                        "gloo_hip_algorithm_set_profiling", "gloo_hip_algorithm_stats",
                        "gloo_hip_algorithm_mode", "gloo_hip_algorithm_create_ws", "gloo_hip_context_mode",
                        "gloo_hip_algorithm_create_streams", "gloo_hip_algorithm_set_streams", "gloo_hip_ipc_stats",
-                       "gloo_hip_ipc_stats_ex")
+                       "gloo_hip_ipc_stats_ex", "gloo_hip_context_agree_on_sharing")
 # the xGMI transport's bound buffers (gloo_amd/include/gloo_amd/gloo_transport.h)
 EXPORTED = EXPORTED + ("gloo_hip_context_create_kv", "gloo_hip_transport_create", "gloo_hip_transport_destroy",
                        "gloo_hip_buffer_create", "gloo_hip_buffer_destroy", "gloo_hip_buffer_send",
@@ -485,11 +486,13 @@ def ipc_stats():
     """This process's pool of cross-process slabs (gloo_amd/include/gloo_amd/ipc.h:
     HIP VMM blocks, never freed while the process lives, reused by size
     class): slabs exported and their bytes, slabs free for reuse, peer slabs
-    mapped, imports made, mappings of exited peers dropped."""
-    out = (ctypes.c_uint64 * 6)()
-    _check(lib.gloo_hip_ipc_stats_ex(out, 6))
+    mapped, imports made, mappings of exited peers dropped; any_size: this
+    process shares slabs of any size (dma-bufs); False once a peer process's
+    import of one was refused (hipIpc handles from then on, below 2 GiB)."""
+    out = (ctypes.c_uint64 * 7)()
+    _check(lib.gloo_hip_ipc_stats_ex(out, 7))
     return {"slabs": out[0], "slab_bytes": out[1], "free": out[2], "peer_slabs_mapped": out[3],
-            "imports": out[4], "dropped": out[5]}
+            "imports": out[4], "dropped": out[5], "any_size": bool(out[6])}
 
 
 def _mode_dict(out):
@@ -520,6 +523,14 @@ class Context:
         out = (ctypes.c_int * 4)()
         _check(lib.gloo_hip_context_mode(self._h, out))
         return _mode_dict(out)
+
+    def agree_on_sharing(self):
+        """Collective: the ranks try a dma-buf import between their processes.
+        True: they share slabs of any size; False: the system refuses such
+        imports, and memory is shared through hipIpc handles, below 2 GiB."""
+        out = ctypes.c_int(0)
+        _check(lib.gloo_hip_context_agree_on_sharing(self._h, ctypes.byref(out)))
+        return bool(out.value)
 
     def close(self):
         if self._h:

@@ -383,6 +383,13 @@ int gloo_hip_interp_batches_ex(const gloo_hip_interp_desc_ex_t* steps, int n, in
   return interpBatches(nullptr, steps, n, defer_out);
 }
 
+int gloo_hip_context_agree_on_sharing(gloo_hip_context_t ctx, int* any_size) {
+  return guarded([&] {
+    GLOO_AMD_ENFORCE(ctx && any_size, "null argument");
+    *any_size = ctx->ctx->agreeOnSharing() ? 1 : 0;
+  });
+}
+
 int gloo_hip_ipc_stats(uint64_t* out) {
   return gloo_hip_ipc_stats_ex(out, 5);
 }
@@ -391,7 +398,7 @@ int gloo_hip_ipc_stats_ex(uint64_t* out, size_t n) {
   return guarded([&] {
     GLOO_AMD_ENFORCE(out, "null argument");
     const gloo_amd::ipc::Stats st = gloo_amd::ipc::stats();
-    const uint64_t v[] = {st.slabs, st.slabBytes, st.free, st.imports, st.opens, st.dropped};
+    const uint64_t v[] = {st.slabs, st.slabBytes, st.free, st.imports, st.opens, st.dropped, st.anySize ? 1u : 0u};
     for (size_t i = 0; i < n && i < sizeof(v) / sizeof(v[0]); i++) out[i] = v[i];
   });
 }

@@ -11,6 +11,7 @@
 
 #include "gloo_amd.h"
 #include "gloo_amd/common.h"
+#include "gloo_amd/ipc.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -36,13 +37,14 @@ Context::Context(int r, int s, std::chrono::milliseconds timeout)
 Context::~Context() {
   if (shmDev_) GLOO_AMD_HIP_RELEASE(hipHostUnregister(shm_));
   if (shm_) ::munmap(shm_, shmBytes_);
+  if (errorWords_.load()) GLOO_AMD_HIP_RELEASE(hipHostFree(errorWords_.load()));
 }
 
 void Context::connect(std::shared_ptr<Store> store, int device) {
   store_ = std::move(store);
   device_ = device;
   countersBytes_ = kMaxLiveInstances * (size_t)size * size * GLOO_HIP_NUM_SLOTS * sizeof(uint64_t);
-  shmBytes_ = sizeof(ShmHeader) + countersBytes_ + ((size_t)size * sizeof(uint32_t) + 63) / 64 * 64;
+  shmBytes_ = sizeof(ShmHeader) + countersBytes_;
   shmBytes_ = (shmBytes_ + 4095) / 4096 * 4096;
   if (rank == 0) {
     std::random_device rd;
@@ -83,8 +85,22 @@ std::atomic<uint64_t>& Context::counter(uint64_t inst, int src, int dst, int slo
 }
 
 void Context::ensureDeviceMapped() {
+  std::lock_guard<std::mutex> lk(mapMutex_);
   if (shmDev_) return;
-  GLOO_AMD_HIP_ALLOC(hipHostRegister(shm_, shmBytes_, hipHostRegisterMapped | hipHostRegisterPortable));
+  // The control block is memory this process already has mapped, which not
+  // every system lets HIP pin (virtual machines refuse it).  Only a device
+  // signal to or from a rank without a device mailbox needs it (executor.h).
+  hipError_t e;
+  {
+    std::lock_guard<std::mutex> allocLock(HipShared::getMutex());
+    e = hipHostRegister(shm_, shmBytes_, hipHostRegisterMapped | hipHostRegisterPortable);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // (a failed registration otherwise shows up at the next launch)
+    throw EnforceNotMet(strcat_("rank ", rank, ": this system cannot pin the node's shared control block for the GPU "
+                                "(hipHostRegister: ", hipGetErrorString(e), "), which device-side signalling between "
+                                "a rank that waits on the host and a rank that waits on the device needs"));
+  }
   void* d = nullptr;
   GLOO_AMD_HIP_CHECK(hipHostGetDevicePointer(&d, shm_, 0));
   shmDev_ = d;
@@ -96,15 +112,36 @@ uint64_t* Context::counterDevicePtr(uint64_t inst, int src, int dst, int slot) {
   return reinterpret_cast<uint64_t*>(static_cast<char*>(shmDev_) + off);
 }
 
+// The error words are this rank's own: its device-side waits write them and
+// its host reads them, so they live in pinned memory of this process.
+void Context::ensureErrorWords() {
+  if (errorWords_.load(std::memory_order_acquire)) return;  // (every call after the first: no lock)
+  std::lock_guard<std::mutex> lk(mapMutex_);
+  if (errorWords_.load(std::memory_order_relaxed)) return;
+  const size_t bytes = ((size_t)size * sizeof(uint32_t) + 63) / 64 * 64;
+  void* h = nullptr;
+  GLOO_AMD_HIP_ALLOC(hipHostMalloc(&h, bytes, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
+  std::memset(h, 0, bytes);
+  void* d = nullptr;
+  const hipError_t e = hipHostGetDevicePointer(&d, h, 0);
+  if (e != hipSuccess) {
+    GLOO_AMD_HIP_RELEASE(hipHostFree(h));
+    GLOO_AMD_HIP_CHECK(e);
+  }
+  errorWordsDev_ = d;
+  errorWords_.store(h, std::memory_order_release);
+}
+
 std::atomic<uint32_t>& Context::errorWord(int r) {
-  auto* base = reinterpret_cast<std::atomic<uint32_t>*>(static_cast<char*>(shm_) + sizeof(ShmHeader) + countersBytes_);
-  return base[r];
+  GLOO_AMD_ENFORCE(r >= 0 && r < size, "no rank ", r);
+  ensureErrorWords();
+  return static_cast<std::atomic<uint32_t>*>(errorWords_.load(std::memory_order_relaxed))[r];
 }
 
 uint32_t* Context::errorWordDevicePtr(int r) {
-  ensureDeviceMapped();
-  const size_t off = reinterpret_cast<char*>(&errorWord(r)) - static_cast<char*>(shm_);
-  return reinterpret_cast<uint32_t*>(static_cast<char*>(shmDev_) + off);
+  GLOO_AMD_ENFORCE(r >= 0 && r < size, "no rank ", r);
+  ensureErrorWords();
+  return static_cast<uint32_t*>(errorWordsDev_) + r;
 }
 
 uint64_t Context::acquireInstance() {
@@ -118,6 +155,14 @@ uint64_t Context::acquireInstance() {
 void Context::releaseInstance(uint64_t inst) {
   std::lock_guard<std::mutex> lk(liveMutex_);
   live_.erase(inst % kMaxLiveInstances);
+}
+
+bool Context::agreeOnSharing() {
+  if (sharing_ < 0)
+    sharing_ = ipc::agreeOnSharing(rank, size, device_, [this](const std::string& tag, const std::vector<char>& mine) {
+      return allgather("sharing/" + tag, mine);
+    }) ? 1 : 0;
+  return sharing_ == 1;
 }
 
 void Context::barrier(const std::string& tag) { (void)allgather("barrier/" + tag, {}); }

@@ -40,8 +40,9 @@ struct ArenaRecord {
   uint64_t ptr;
   uint64_t bytes;
   uint64_t slabId;           // DEVICE workspace shared with other processes: the pool slab (ipc.h)
-  int32_t host;              // HOST workspace: the arena is the shm segment `shm`
-  char shm[60];
+  int32_t host;              // HOST workspace: pinned host memory, `hostIpc` for a peer process
+  int32_t pad0;
+  hipIpcMemHandle_t hostIpc;
   int32_t deviceSignal;      // this rank signals with stream-ordered kernels
   int32_t hasMailbox;        // ... into device-resident mailboxes
   uint64_t mailboxPtr;
@@ -203,62 +204,45 @@ uint64_t exchangeHash(const Plan& p) {
 
 }  // namespace
 
-// A pinned host-memory segment every rank of the node can map (HOST workspace).
+// Pinned host memory every rank of the node can address from its GPU (HOST
+// workspace): hipHostMalloc memory of its owner.  The other ranks of the
+// owner's process reach it by its address, ranks of other processes open its
+// hipIpc handle (memory a process already has mapped, a named segment for
+// one, cannot be pinned on every system).
 struct PlanExecutor::HostShm {
-  std::string name;
-  void* host = nullptr;
-  void* dev = nullptr;
+  void* host = nullptr;  // the owner's allocation
+  void* dev = nullptr;   // as this rank's GPU addresses it
   size_t bytes = 0;
-  bool owner = false;
+  bool imported = false;  // a peer process's, opened here
+  hipIpcMemHandle_t handle;
 
-  static std::unique_ptr<HostShm> create(size_t bytes) {
+  // shared: a rank of another process opens it too
+  static std::unique_ptr<HostShm> create(size_t bytes, bool shared) {
     auto h = std::make_unique<HostShm>();
-    std::random_device rd;
-    h->name = strcat_("/gloo_amd_ws_", ::getpid(), "_", rd(), rd());
     h->bytes = bytes;
-    h->owner = true;
-    const int fd = ::shm_open(h->name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
-    GLOO_AMD_ENFORCE(fd >= 0, "shm_open(create) failed for ", h->name);
-    const bool sized = ::ftruncate(fd, (off_t)bytes) == 0;
-    if (sized) h->host = ::mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    ::close(fd);
-    if (!sized || h->host == MAP_FAILED) {
+    std::memset(&h->handle, 0, sizeof(h->handle));
+    GLOO_AMD_ENFORCE(!shared || bytes < (size_t(2) << 30), "a host workspace of ", bytes, " B shared between "
+                     "processes: memory shared between processes stays below 2 GiB");
+    GLOO_AMD_HIP_ALLOC(hipHostMalloc(&h->host, bytes, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
+    hipError_t e = hipHostGetDevicePointer(&h->dev, h->host, 0);
+    if (e == hipSuccess && shared) e = hipIpcGetMemHandle(&h->handle, h->host);
+    if (e != hipSuccess) {
+      GLOO_AMD_HIP_RELEASE(hipHostFree(h->host));
       h->host = nullptr;
-      ::shm_unlink(h->name.c_str());
-      throw EnforceNotMet(strcat_("cannot map a ", bytes, "-byte host workspace"));
+      GLOO_AMD_HIP_CHECK(e);
     }
-    h->map();
     return h;
   }
-  static std::unique_ptr<HostShm> open(const std::string& name, size_t bytes) {
+  static std::unique_ptr<HostShm> open(const hipIpcMemHandle_t& handle, size_t bytes) {
     auto h = std::make_unique<HostShm>();
-    h->name = name;
     h->bytes = bytes;
-    const int fd = ::shm_open(name.c_str(), O_RDWR, 0600);
-    GLOO_AMD_ENFORCE(fd >= 0, "shm_open failed for ", name);
-    h->host = ::mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    ::close(fd);
-    if (h->host == MAP_FAILED) {
-      h->host = nullptr;
-      throw EnforceNotMet(strcat_("cannot map host workspace ", name));
-    }
-    h->map();
+    h->imported = true;
+    GLOO_AMD_HIP_ALLOC(hipIpcOpenMemHandle(&h->dev, handle, hipIpcMemLazyEnablePeerAccess));
     return h;
-  }
-  void map() {
-    GLOO_AMD_HIP_ALLOC(hipHostRegister(host, bytes, hipHostRegisterMapped | hipHostRegisterPortable));
-    GLOO_AMD_HIP_CHECK(hipHostGetDevicePointer(&dev, host, 0));
-  }
-  void unlink() {
-    if (owner && !name.empty()) ::shm_unlink(name.c_str());
-    owner = false;
   }
   ~HostShm() {
-    if (host) {
-      GLOO_AMD_HIP_RELEASE(hipHostUnregister(host));
-      ::munmap(host, bytes);
-    }
-    unlink();
+    if (imported && dev) GLOO_AMD_HIP_RELEASE(hipIpcCloseMemHandle(dev));
+    if (host) GLOO_AMD_HIP_RELEASE(hipHostFree(host));
   }
 };
 
@@ -395,7 +379,7 @@ void PlanExecutor::mapPeers(const std::vector<std::vector<char>>& arenas, const 
     if (!sendPeers.count(peer)) continue;
     if (pr.host && pr.pid != ctx_->pid()) {
       // another process's host workspace: map the same pages here
-      peerShm_.push_back(HostShm::open(std::string(pr.shm), pr.bytes));
+      peerShm_.push_back(HostShm::open(pr.hostIpc, pr.bytes));
       peers_[peer].base = static_cast<char*>(peerShm_.back()->dev);
     } else if (pr.host || pr.pid == ctx_->pid()) {
       // same process: registered portable (host) or peer-accessible (device)
@@ -453,8 +437,15 @@ void PlanExecutor::mapPeers(const std::vector<std::vector<char>>& arenas, const 
 // store flavours are fixed: executor.h, each from a measured A/B.)
 void PlanExecutor::configureDeviceLaunches() {
   const int me = ctx_->rank, P = ctx_->size;
-  (void)me;
-  (void)ctx_->counterDevicePtr(inst_, 0, 0, 0);  // register the control block now
+  // A plan peer without a device mailbox (a rank that waits on the host) is
+  // signalled and waited for through the control block's counters: register
+  // the block now, outside any enqueue or capture.  Peers with mailboxes
+  // never touch it from the device.
+  for (int peer = 0; peer < P; peer++)
+    if (peer != me && peers_[peer].pid >= 0 && !mailboxWith(peer)) {
+      (void)ctx_->counterDevicePtr(inst_, me, peer, 0);
+      break;
+    }
   ctx_->errorWord(me).store(0);
   const size_t tickets = std::max<size_t>(256, (size_t)P * GLOO_HIP_NUM_SLOTS * sizeof(unsigned));
   GLOO_AMD_HIP_ALLOC(hipMalloc(&ticket_, tickets));
@@ -667,6 +658,13 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
                        "and the call's arguments must be equal on every rank");
     }
   }
+  // a context that spans processes settles how they share device memory
+  // before its first slab (every rank sees the same records: collective)
+  for (int r = 0; r < P; r++)
+    if (where[r].pid != ctx_->pid()) {
+      (void)ctx_->agreeOnSharing();
+      break;
+    }
   peers_.resize(P);
   bool sharesDeviceInProcess = false;
   for (int peer : planPeers) {
@@ -712,7 +710,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
   const size_t arenaBytes = arenaBytesOf(plan_);
   arenaBytes_ = arenaBytes;
   if (hostArena_) {
-    arenaShm_ = HostShm::create(arenaBytes);
+    arenaShm_ = HostShm::create(arenaBytes, crossProcess_);
     arena_ = static_cast<char*>(arenaShm_->dev);
   } else if (crossProcess_) {
     GLOO_AMD_TRACE_PHASE("acquiring a slab of ", arenaBytes, " B fine=", fineArena_);
@@ -807,8 +805,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
   }
   if (hostArena_) {
     rec.host = 1;
-    GLOO_AMD_ENFORCE(arenaShm_->name.size() < sizeof(rec.shm), "shm name too long");
-    std::memcpy(rec.shm, arenaShm_->name.c_str(), arenaShm_->name.size() + 1);
+    rec.hostIpc = arenaShm_->handle;
   } else if (arenaSlab_) {
     rec.slabId = arenaSlab_->id;  // exported once, when the pool allocated the slab
   }
@@ -860,7 +857,6 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
       GLOO_AMD_ENFORCE(ready[r].empty(), "rank ", r, " could not set up its side of the collective: ",
                        std::string(ready[r].begin(), ready[r].end()));
   }
-  if (arenaShm_) arenaShm_->unlink();  // every peer has mapped it by now
 }
 
 PlanExecutor::~PlanExecutor() { release(); }
@@ -886,8 +882,10 @@ void PlanExecutor::release() {
         if (peerMailboxIpc_[q]) ipc::unimport(peerMailbox_[q]);
       peers_.clear();
       peerMailbox_.clear();
-      ctx_->barrier(strcat_("inst", inst_, "/closed"));
+      // a peer process's HOST workspace is closed here before its owner,
+      // past the barrier, frees it (a hipIpc handle names an address)
       peerShm_.clear();
+      ctx_->barrier(strcat_("inst", inst_, "/closed"));
       if (arenaShm_) {
         arenaShm_.reset();
       } else if (arenaSlab_) {

@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstddef>
 #include <cstdlib>
@@ -125,6 +126,9 @@ struct Reply {
   int32_t ok;
   int32_t pad;
   uint64_t bytes;
+  hipIpcMemHandle_t slab;  // a pool slab: its hipIpc handle (no fd attached then)
+  int32_t hasSlab;
+  int32_t pad2;
 };
 
 void socketName(int pid, uint64_t inc, sockaddr_un* a, socklen_t* len) {
@@ -144,16 +148,24 @@ void serveConnection(int c) {
   if (getsockopt(c, SOL_SOCKET, SO_PEERCRED, &cred, &cl) != 0 || cred.uid != ::getuid()) return;
   uint64_t id = 0;
   if (::recv(c, &id, sizeof(id), MSG_WAITALL) != (ssize_t)sizeof(id)) return;
-  Reply r{0, 0, 0};
+  Reply r;
+  std::memset(&r, 0, sizeof(r));
   int fd = -1;
+  bool slab = false;
   {
     Pool& p = Pool::get();
     std::lock_guard<std::mutex> lk(p.m);
     for (const auto& s : p.slabs)
       if (s->id == id) {
-        fd = s->fd;
         r.ok = 1;
         r.bytes = s->bytes;
+        if (s->handle) {
+          fd = s->fd;
+        } else {
+          r.slab = s->ipc;
+          r.hasSlab = 1;
+          slab = true;
+        }
       }
     auto e = p.exports.find(id);
     if (e != p.exports.end()) {
@@ -164,7 +176,7 @@ void serveConnection(int c) {
     // a duplicate taken under the lock: an export may be closed
     // (unexportRange) while the reply is on its way
     if (fd >= 0) fd = ::fcntl(fd, F_DUPFD_CLOEXEC, 0);
-    if (fd < 0) r.ok = 0;
+    if (fd < 0 && !slab) r.ok = 0;
   }
   iovec iov{&r, sizeof(r)};
   msghdr h;
@@ -220,7 +232,7 @@ void ensureServer() {
 }
 
 // The dma-buf fd of slab `id` of process (pid, inc); its size class in *bytes.
-int fetchFd(int pid, uint64_t inc, uint64_t id, size_t* bytes) {
+int fetchFd(int pid, uint64_t inc, uint64_t id, size_t* bytes, hipIpcMemHandle_t* slab = nullptr) {
   sockaddr_un a;
   socklen_t len;
   socketName(pid, inc, &a, &len);
@@ -239,7 +251,8 @@ int fetchFd(int pid, uint64_t inc, uint64_t id, size_t* bytes) {
   timeval tv{30, 0};
   (void)setsockopt(c, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
   const bool sent = ::send(c, &id, sizeof(id), MSG_NOSIGNAL) == (ssize_t)sizeof(id);
-  Reply r{0, 0, 0};
+  Reply r;
+  std::memset(&r, 0, sizeof(r));
   iovec iov{&r, sizeof(r)};
   msghdr h;
   std::memset(&h, 0, sizeof(h));
@@ -254,6 +267,12 @@ int fetchFd(int pid, uint64_t inc, uint64_t id, size_t* bytes) {
     for (cmsghdr* cm = CMSG_FIRSTHDR(&h); cm; cm = CMSG_NXTHDR(&h, cm))
       if (cm->cmsg_level == SOL_SOCKET && cm->cmsg_type == SCM_RIGHTS) std::memcpy(&fd, CMSG_DATA(cm), sizeof(int));
   ::close(c);
+  if (slab && got == (ssize_t)sizeof(r) && r.ok && r.hasSlab) {
+    if (fd >= 0) ::close(fd);
+    *slab = r.slab;
+    *bytes = r.bytes;
+    return -1;
+  }
   if (got != (ssize_t)sizeof(r) || !r.ok || fd < 0) {
     if (fd >= 0) ::close(fd);
     GLOO_AMD_ENFORCE(false, "pid ", pid, " did not hand over its slab ", id, " (", got != (ssize_t)sizeof(r) ? "no reply" : "unknown slab", ")");
@@ -289,6 +308,21 @@ hipError_t importFd(int fd, hipMemGenericAllocationHandle_t* h) {
   return e;
 }
 
+// Closes a peer slab's mapping: a VMM import (handle set) or an opened hipIpc
+// handle.  (A VMM range stays reserved, never mapped again: ipc.h.)
+void closeMapping(Pool::Mapping& m) {
+  if (m.handle) {
+    GLOO_AMD_HIP_RELEASE(hipMemUnmap(m.ptr, m.bytes));
+    GLOO_AMD_HIP_RELEASE(hipMemRelease(m.handle));
+  } else {
+    GLOO_AMD_HIP_RELEASE(hipIpcCloseMemHandle(m.ptr));
+  }
+}
+
+// Whether peers can import this system's dma-bufs (ipc.h agreeOnSharing):
+// assumed until a peer process reports a refused import, then never again.
+std::atomic<bool> g_dmabuf{true};
+
 // At process exit, before the HIP runtime tears down (atexit handlers run in
 // reverse order of registration, and this one is registered after the
 // runtime's first use): unmap and release every mapping and slab, so the
@@ -296,11 +330,9 @@ hipError_t importFd(int fd, hipMemGenericAllocationHandle_t* h) {
 void releaseAllAtExit() {
   Pool& p = Pool::get();
   std::lock_guard<std::mutex> lk(p.m);
-  for (auto& kv : p.imports) {
-    (void)hipMemUnmap(kv.second.ptr, kv.second.bytes);
-    (void)hipMemRelease(kv.second.handle);
-  }
+  for (auto& kv : p.imports) closeMapping(kv.second);
   for (auto& s : p.slabs) {
+    if (!s->handle) continue;  // a plain allocation peers open by hipIpc handle: it goes with the process
     (void)hipMemUnmap(s->ptr, s->bytes);
     (void)hipMemRelease(s->handle);
     if (s->fd >= 0) ::close(s->fd);
@@ -342,6 +374,7 @@ Remote describe(const Slab& s) {
 
 Slab* acquire(int device, size_t bytes, bool fine) {
   const size_t want = sizeClass(bytes);
+  const bool vmm = g_dmabuf.load();
   ensureServer();
   registerAtExit();
   Pool& p = Pool::get();
@@ -354,7 +387,7 @@ Slab* acquire(int device, size_t bytes, bool fine) {
   size_t best = p.free.size();
   for (size_t i = 0; i < p.free.size(); i++) {
     const Slab* s = p.free[i];
-    if (s->device == device && s->fine == fine && s->bytes >= bytes &&
+    if (s->device == device && s->fine == fine && s->bytes >= bytes && (s->handle != nullptr) == vmm &&
         (best == p.free.size() || s->bytes < p.free[best]->bytes))
       best = i;
   }
@@ -368,8 +401,14 @@ Slab* acquire(int device, size_t bytes, bool fine) {
   s->bytes = want;
   s->device = device;
   s->fine = fine;
+  // hipIpcOpenMemHandle of 2 GiB or more does not return
+  GLOO_AMD_ENFORCE(vmm || want < (size_t(2) << 30), "a cross-process slab of ", want, " B: peer processes cannot import "
+                   "this system's dma-bufs, and the hipIpc handles used instead stay below 2 GiB");
   const hipMemAllocationProp prop = propFor(device, fine);
-  const hipError_t ce = hipMemCreate(&s->handle, want, &prop, 0);
+  void* block = nullptr;
+  // (hipIpc: a plain allocation, uncached where peers write it, as the VMM type is)
+  const hipError_t ce = vmm ? hipMemCreate(&s->handle, want, &prop, 0)
+                            : hipExtMallocWithFlags(&block, want, fine ? hipDeviceMallocUncached : hipDeviceMallocDefault);
   if (ce == hipErrorOutOfMemory || ce == hipErrorMemoryAllocation) {
     (void)hipGetLastError();
     size_t held = 0, idle = 0, nidle = 0;
@@ -383,6 +422,19 @@ Slab* acquire(int device, size_t bytes, bool fine) {
                                 "process lives (gloo_amd/include/gloo_amd/ipc.h)"));
   }
   GLOO_AMD_HIP_ALLOC(ce);
+  std::memset(&s->ipc, 0, sizeof(s->ipc));
+  if (!vmm) {
+    const hipError_t he = hipIpcGetMemHandle(&s->ipc, block);
+    if (he != hipSuccess) {
+      (void)hipFree(block);  // (never shared, never read by a kernel)
+      GLOO_AMD_HIP_CHECK(he);
+    }
+    s->ptr = static_cast<char*>(block);
+    s->devices = ~uint64_t(0);  // a plain allocation: peer access covers it
+    s->id = p.nextId++;
+    p.slabs.push_back(std::move(s));
+    return p.slabs.back().get();
+  }
   try {
     void* va = freshRange(want);
     mapAt(va, want, s->handle, device);
@@ -418,8 +470,7 @@ void dropDeadImports(Pool& p) {
       ++it;
       continue;
     }
-    GLOO_AMD_HIP_RELEASE(hipMemUnmap(it->second.ptr, it->second.bytes));
-    GLOO_AMD_HIP_RELEASE(hipMemRelease(it->second.handle));
+    closeMapping(it->second);
     p.dropped++;
     it = p.imports.erase(it);
   }
@@ -461,8 +512,7 @@ void* import(const Remote& r, size_t bytes, int device) {
       }
       // a new process reusing a dead one's pid: its mapping is of no use (the
       // range stays reserved, never mapped again)
-      GLOO_AMD_HIP_RELEASE(hipMemUnmap(it->second.ptr, it->second.bytes));
-      GLOO_AMD_HIP_RELEASE(hipMemRelease(it->second.handle));
+      closeMapping(it->second);
       p.dropped++;
       p.imports.erase(it);
     }
@@ -470,8 +520,28 @@ void* import(const Remote& r, size_t bytes, int device) {
   // The pool's lock is NOT held across the request: the exporter may be
   // importing from this process at the same moment, and its request is
   // answered by this process's fd server, which takes the lock.
+  // One open at a time: two threads of this process never open the same
+  // slab twice (a hipIpc handle opened twice showed stale pages).  Not the
+  // pool's lock, which this process's server takes to answer its peers.
+  static std::mutex openMutex;
+  std::lock_guard<std::mutex> openLock(openMutex);
+  {
+    std::lock_guard<std::mutex> lk(p.m);
+    auto it = p.imports.find(key);
+    if (it != p.imports.end() && it->second.incarnation == r.incarnation) {
+      const uint64_t bit = device < 64 ? uint64_t(1) << device : 0;
+      if (bit && !(it->second.devices & bit)) {
+        GLOO_AMD_HIP_CHECK(allowAccess(it->second.ptr, it->second.bytes, device));
+        it->second.devices |= bit;
+      }
+      it->second.users++;
+      return it->second.ptr;
+    }
+  }
   size_t slabBytes = 0;
-  const int fd = fetchFd(r.pid, r.incarnation, r.id, &slabBytes);
+  hipIpcMemHandle_t ih;
+  std::memset(&ih, 0, sizeof(ih));
+  const int fd = fetchFd(r.pid, r.incarnation, r.id, &slabBytes, &ih);
   GLOO_AMD_ENFORCE(slabBytes >= bytes, "slab ", r.id, " of pid ", r.pid, " holds ", slabBytes, " B, ", bytes,
                    " B expected");
   DeviceScope ds(device);
@@ -483,21 +553,27 @@ void* import(const Remote& r, size_t bytes, int device) {
   // importFd closes it unless the runtime already did — and a number the
   // runtime closed may already name another thread's file (an fd server's
   // accepted socket), so only while it still names this dma-buf.
-  GLOO_AMD_HIP_ALLOC(importFd(fd, &h));
   void* va = nullptr;
-  try {
-    va = freshRange(slabBytes);
-    mapAt(va, slabBytes, h, device);
-  } catch (...) {
-    (void)hipMemRelease(h);
-    throw;
+  if (fd < 0) {
+    // the owner shares through hipIpc handles: opened once per (process,
+    // slab) and kept, like a VMM mapping
+    GLOO_AMD_HIP_ALLOC(hipIpcOpenMemHandle(&va, ih, hipIpcMemLazyEnablePeerAccess));
+  } else {
+    GLOO_AMD_HIP_ALLOC(importFd(fd, &h));
+    try {
+      va = freshRange(slabBytes);
+      mapAt(va, slabBytes, h, device);
+    } catch (...) {
+      (void)hipMemRelease(h);
+      throw;
+    }
   }
   std::lock_guard<std::mutex> lk(p.m);
   auto it = p.imports.find(key);
   if (it != p.imports.end() && it->second.incarnation == r.incarnation) {
     // another thread of this process mapped it meanwhile: keep that one
-    GLOO_AMD_HIP_RELEASE(hipMemUnmap(va, slabBytes));
-    GLOO_AMD_HIP_RELEASE(hipMemRelease(h));
+    Pool::Mapping mine{r.incarnation, va, slabBytes, 0, h, 0};
+    closeMapping(mine);
     const uint64_t bit = device < 64 ? uint64_t(1) << device : 0;
     if (bit && !(it->second.devices & bit)) {
       GLOO_AMD_HIP_CHECK(allowAccess(it->second.ptr, it->second.bytes, device));
@@ -507,7 +583,7 @@ void* import(const Remote& r, size_t bytes, int device) {
     return it->second.ptr;
   }
   p.opens++;
-  p.imports[key] = {r.incarnation, va, slabBytes, 1, h, device < 64 ? uint64_t(1) << device : 0};
+  p.imports[key] = {r.incarnation, va, slabBytes, 1, h, h ? (device < 64 ? uint64_t(1) << device : 0) : ~uint64_t(0)};
   return va;
 }
 
@@ -551,7 +627,7 @@ ExportDmabufFn exportDmabuf() {
 }  // namespace
 
 bool exportRange(const void* ptr, size_t bytes, RangeExport* out) {
-  ExportDmabufFn f = exportDmabuf();
+  ExportDmabufFn f = g_dmabuf.load() ? exportDmabuf() : nullptr;  // (else: the caller's landing slab)
   if (!f || !ptr || !bytes) return false;
   int fd = -1;
   uint64_t off = 0;
@@ -610,6 +686,80 @@ void unimportRange(RangeImport* m) {
   *m = RangeImport();
 }
 
+bool dmabufSharing() { return g_dmabuf.load(); }
+
+bool agreeOnSharing(int rank, int size, int device, const Exchange& exchange) {
+  // Round 1: every rank exports a one-granule block (never mapped) under its
+  // server, unless this process already knows the answer is no.
+  struct Offer {
+    int32_t pid, usable;
+    uint64_t incarnation, id;
+  } mine;
+  std::memset(&mine, 0, sizeof(mine));
+  mine.pid = (int32_t)::getpid();
+  mine.incarnation = incarnation();
+  hipMemGenericAllocationHandle_t h = nullptr;
+  if (g_dmabuf.load()) {
+    ensureServer();
+    registerAtExit();
+    DeviceScope ds(device);
+    const hipMemAllocationProp prop = propFor(device, false);
+    int fd = -1;
+    if (hipMemCreate(&h, kGranule, &prop, 0) == hipSuccess &&
+        hipMemExportToShareableHandle(&fd, h, hipMemHandleTypePosixFileDescriptor, 0) == hipSuccess && fd >= 0) {
+      Pool& p = Pool::get();
+      std::lock_guard<std::mutex> lk(p.m);
+      mine.id = p.nextId++;
+      p.exports[mine.id] = {fd, kGranule};
+      mine.usable = 1;
+    }
+    (void)hipGetLastError();
+  }
+  const char* mb = reinterpret_cast<const char*>(&mine);
+  const auto offers = exchange("offer", std::vector<char>(mb, mb + sizeof(mine)));
+  // Round 2: import the block of the next rank that lives in another process.
+  int32_t ok = mine.usable;
+  for (int k = 1; ok && k < size; k++) {
+    Offer o;
+    const auto& v = offers.at((size_t)((rank + k) % size));
+    GLOO_AMD_ENFORCE(v.size() == sizeof(o), "bad sharing offer");
+    std::memcpy(&o, v.data(), sizeof(o));
+    if (!o.usable) ok = 0;
+    if (!o.usable || o.pid == mine.pid) continue;
+    try {
+      size_t bytes = 0;
+      const int fd = fetchFd(o.pid, o.incarnation, o.id, &bytes);
+      DeviceScope ds(device);
+      hipMemGenericAllocationHandle_t got = nullptr;
+      if (importFd(fd, &got) == hipSuccess) {
+        (void)hipMemRelease(got);
+      } else {
+        ok = 0;
+      }
+      (void)hipGetLastError();
+    } catch (const std::exception&) {
+      ok = 0;
+    }
+    break;
+  }
+  const char* ob = reinterpret_cast<const char*>(&ok);
+  const auto verdicts = exchange("verdict", std::vector<char>(ob, ob + sizeof(ok)));
+  bool all = true;
+  for (const auto& v : verdicts) {
+    int32_t x = 0;
+    if (v.size() == sizeof(x)) std::memcpy(&x, v.data(), sizeof(x));
+    all = all && x == 1;
+  }
+  if (mine.id) {
+    RangeExport e;
+    e.id = mine.id;
+    unexportRange(e);
+  }
+  if (h) (void)hipMemRelease(h);
+  if (!all) g_dmabuf.store(false);
+  return all;
+}
+
 Stats stats() {
   Pool& p = Pool::get();
   std::lock_guard<std::mutex> lk(p.m);
@@ -620,6 +770,7 @@ Stats stats() {
   s.imports = p.imports.size();
   s.opens = p.opens;
   s.dropped = p.dropped;
+  s.anySize = g_dmabuf.load();
   return s;
 }
 

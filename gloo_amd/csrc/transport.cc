@@ -97,6 +97,11 @@ bool pollUntil(F done, const std::atomic<bool>* abort, std::chrono::milliseconds
 std::atomic<uint64_t> g_staged{0};
 std::atomic<uint64_t> g_landing{0};
 
+// Transport blocks in pinned memory, between rank 0's allocation and the
+// other ranks of the process taking their hold (Device::Device).
+std::mutex g_pinnedMutex;
+std::map<std::string, std::shared_ptr<void>> g_pinnedBlocks;
+
 // A named node shared-memory segment of `bytes` (zero-filled, pages on first
 // touch), mapped read-write.
 void* createSegment(const std::string& name, size_t bytes) {
@@ -110,6 +115,17 @@ void* createSegment(const std::string& name, size_t bytes) {
     GLOO_AMD_ENFORCE(false, "landing segment of ", bytes, " B: ftruncate/mmap failed");
   }
   return m;
+}
+
+// An arrival published by the host, in stream order (SendBuffer::send).
+struct Arrival {
+  std::atomic<uint64_t>* count;
+  uint64_t k;
+};
+void publishArrival(void* p) {
+  Arrival* a = static_cast<Arrival*>(p);
+  a->count->store(a->k, std::memory_order_release);
+  delete a;
 }
 
 class SendBuffer : public Buffer {
@@ -173,7 +189,16 @@ class SendBuffer : public Buffer {
     }
     // (arrivals are published from the device: 9.1 us one way at 1 KiB
     // against 26.4 us through a stream host function)
-    if (srcDevice_ && dstDevice_ && length) {
+    if (!channelDev_) {
+      // the GPU cannot address the block the processes share: the bytes move
+      // by a stream-ordered copy and a host function behind it publishes the
+      // arrival (the executor's host-signalled SENDs do the same)
+      if (length) GLOO_AMD_HIP_CHECK(hipMemcpyAsync(dst, src, length, hipMemcpyDefault, s));
+      auto* a = new Arrival{&channel_->count, k};
+      const hipError_t e = hipLaunchHostFunc(s, publishArrival, a);
+      if (e != hipSuccess) delete a;
+      GLOO_AMD_HIP_CHECK(e);
+    } else if (srcDevice_ && dstDevice_ && length) {
       // device to device: one copy kernel, the arrival published by its last workgroup
       checkRc(launchCopySignal(dst, src, length, channelDev_, Seq{k, 0}, ticket_, nullptr,
                                copySignalGrid(length, sameGpu_ ? kSendBlocksLocal : kSendBlocks), s),
@@ -227,8 +252,15 @@ class SendBuffer : public Buffer {
       landing_ = static_cast<char*>(m);
       viaLanding_ = true;
       if (srcDevice_) {
-        GLOO_AMD_HIP_ALLOC(hipHostRegister(landing_, r.size, hipHostRegisterPortable));
-        landingRegistered_ = true;
+        // (pinned where the system allows: the copies go through the runtime's
+        // staging otherwise)
+        hipError_t e;
+        {
+          std::lock_guard<std::mutex> allocLock(HipShared::getMutex());
+          e = hipHostRegister(landing_, r.size, hipHostRegisterPortable);
+        }
+        landingRegistered_ = e == hipSuccess;
+        if (!landingRegistered_) (void)hipGetLastError();
       }
     } else if (r.exported) {
       // device memory of another process: its dma-buf range, mapped here
@@ -256,7 +288,7 @@ class SendBuffer : public Buffer {
     }
     if (srcDevice_ || dstDevice_) {
       channelDev_ = dev_->channelDevicePtr(ctx.rank, peer_, r.channel);
-      if (srcDevice_ && dstDevice_) {
+      if (channelDev_ && srcDevice_ && dstDevice_) {
         GLOO_AMD_HIP_ALLOC(hipMalloc(reinterpret_cast<void**>(&ticket_), sizeof(unsigned)));
         // zeroed on the transport's stream, ahead of the first copy kernel: a
         // plain hipMemset goes to the null stream, which a non-blocking
@@ -422,8 +454,26 @@ Device::Device(std::shared_ptr<Context> ctx, hipStream_t stream) : ctx_(std::mov
   blockBytes_ = 4096 + P * P * kChannels * sizeof(Channel) + P * P * kAnnouncements * sizeof(Announcement) + P * 64 +
                 P * P * kChannels * kMsgRing * sizeof(MsgRecord);
   blockBytes_ = (blockBytes_ + 4095) / 4096 * 4096;
+  // Ranks of ONE process share a block of pinned host memory by its address
+  // (hipHostMalloc: the GPU addresses it from the start).  Ranks of several
+  // processes share a named segment, which channelDevicePtr registers with
+  // HIP where the system can pin memory a process already has mapped.
+  const int32_t pid = ctx_->pid();
+  const char* pidBytes = reinterpret_cast<const char*>(&pid);
+  const auto pids = ctx_->allgather(strcat_("tdev", inst_, "/pid"), std::vector<char>(pidBytes, pidBytes + sizeof(pid)));
+  for (const auto& v : pids)
+    if (v.size() != sizeof(pid) || std::memcmp(v.data(), &pid, sizeof(pid)) != 0) blockPinned_ = false;
+  if (!blockPinned_) (void)ctx_->agreeOnSharing();  // before the first receive buffer's export or landing slab
   std::string name;
-  if (ctx_->rank == 0) {
+  if (ctx_->rank == 0 && blockPinned_) {
+    void* m = nullptr;
+    GLOO_AMD_HIP_ALLOC(hipHostMalloc(&m, blockBytes_, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
+    std::memset(m, 0, blockBytes_);
+    blockHold_ = std::shared_ptr<void>(m, [](void* q) { GLOO_AMD_HIP_RELEASE(hipHostFree(q)); });
+    name = strcat_(reinterpret_cast<uintptr_t>(m));
+    std::lock_guard<std::mutex> lk(g_pinnedMutex);
+    g_pinnedBlocks[name] = blockHold_;
+  } else if (ctx_->rank == 0) {
     std::random_device rd;
     name = strcat_("/gloo_amd_t_", ctx_->pid(), "_", rd(), rd());
     const int fd = ::shm_open(name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
@@ -436,7 +486,17 @@ Device::Device(std::shared_ptr<Context> ctx, hipStream_t stream) : ctx_(std::mov
   const auto names = ctx_->allgather(strcat_("tdev", inst_, "/block"),
                                      ctx_->rank == 0 ? std::vector<char>(name.begin(), name.end())
                                                      : std::vector<char>{});
-  if (ctx_->rank != 0) {
+  if (blockPinned_) {
+    name.assign(names[0].begin(), names[0].end());
+    {
+      std::lock_guard<std::mutex> lk(g_pinnedMutex);
+      auto it = g_pinnedBlocks.find(name);
+      if (it != g_pinnedBlocks.end()) blockHold_ = it->second;  // held until this rank's transport goes
+    }
+    GLOO_AMD_ENFORCE(blockHold_ != nullptr, "transport block: rank 0's pinned block is not in this process");
+    block_ = blockHold_.get();
+    GLOO_AMD_HIP_CHECK(hipHostGetDevicePointer(&blockDev_, block_, 0));
+  } else if (ctx_->rank != 0) {
     name.assign(names[0].begin(), names[0].end());
     const int fd = ::shm_open(name.c_str(), O_RDWR, 0600);
     GLOO_AMD_ENFORCE(fd >= 0, "shm_open failed for ", name);
@@ -445,7 +505,12 @@ Device::Device(std::shared_ptr<Context> ctx, hipStream_t stream) : ctx_(std::mov
     GLOO_AMD_ENFORCE(block_ != MAP_FAILED, "transport block: mmap failed");
   }
   ctx_->barrier(strcat_("tdev", inst_, "/mapped"));
-  if (ctx_->rank == 0) ::shm_unlink(name.c_str());  // every rank has it mapped now
+  if (ctx_->rank == 0 && blockPinned_) {
+    std::lock_guard<std::mutex> lk(g_pinnedMutex);
+    g_pinnedBlocks.erase(name);  // every rank holds it now
+  } else if (ctx_->rank == 0) {
+    ::shm_unlink(name.c_str());  // every rank has it mapped now
+  }
   channelUsed_.assign(P, std::vector<bool>(kChannels, false));
 }
 
@@ -461,8 +526,12 @@ Device::~Device() {
         uint32_t ready = 2;
         if (a.state.compare_exchange_strong(ready, 3) && a.name[0]) ::shm_unlink(a.name);
       }
-    if (blockDev_) GLOO_AMD_HIP_RELEASE(hipHostUnregister(block_));
-    ::munmap(block_, blockBytes_);
+    if (blockPinned_) {
+      blockHold_.reset();  // freed with the last rank's transport
+    } else {
+      if (blockDev_) GLOO_AMD_HIP_RELEASE(hipHostUnregister(block_));
+      ::munmap(block_, blockBytes_);
+    }
   }
   ctx_->releaseInstance(inst_);
 }
@@ -517,8 +586,18 @@ Device::MsgRecord& Device::msgRecord(int src, int dst, int idx, uint64_t k) {
 uint64_t* Device::channelDevicePtr(int src, int dst, int idx) {
   {
     std::lock_guard<std::mutex> lk(m_);
+    if (blockUnpinnable_) return nullptr;
     if (!blockDev_) {
-      GLOO_AMD_HIP_ALLOC(hipHostRegister(block_, blockBytes_, hipHostRegisterMapped | hipHostRegisterPortable));
+      hipError_t e;
+      {
+        std::lock_guard<std::mutex> allocLock(HipShared::getMutex());
+        e = hipHostRegister(block_, blockBytes_, hipHostRegisterMapped | hipHostRegisterPortable);
+      }
+      if (e != hipSuccess) {
+        (void)hipGetLastError();  // (a failed registration otherwise shows up at the next launch)
+        blockUnpinnable_ = true;
+        return nullptr;
+      }
       void* d = nullptr;
       GLOO_AMD_HIP_CHECK(hipHostGetDevicePointer(&d, block_, 0));
       blockDev_ = d;

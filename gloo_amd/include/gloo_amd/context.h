@@ -59,12 +59,21 @@ class Context : public std::enable_shared_from_this<Context> {
 
   // Counter for messages src -> dst on `slot` of instance `inst`.
   std::atomic<uint64_t>& counter(uint64_t inst, int src, int dst, int slot);
-  // The same counter as a GPU-addressable pointer (the control block is
-  // registered with hipHostRegister on first use).
+  // The same counter as a GPU-addressable pointer: the control block is
+  // registered with hipHostRegister on first use, and the call raises where
+  // the system cannot pin memory a process already has mapped.  Ranks that
+  // signal each other through device mailboxes never need it (executor.h).
   uint64_t* counterDevicePtr(uint64_t inst, int src, int dst, int slot);
-  // Per-rank error word written by device-side waits that time out.
+  // Per-rank error word written by device-side waits that time out (pinned
+  // memory of this process, allocated on first use: a rank's device and its
+  // host are its only users).
   std::atomic<uint32_t>& errorWord(int r);
   uint32_t* errorWordDevicePtr(int r);
+
+  // Collective, once per context (later calls return the answer): the ranks
+  // settle how their processes share device memory (ipc.h agreeOnSharing).
+  // True: dma-bufs, any size; false: hipIpc handles, below 2 GiB.
+  bool agreeOnSharing();
 
   // Store-based barrier among all ranks (setup / teardown only).
   void barrier(const std::string& tag);
@@ -86,7 +95,12 @@ class Context : public std::enable_shared_from_this<Context> {
   size_t shmBytes_ = 0;
   size_t countersBytes_ = 0;
   void ensureDeviceMapped();
+  std::mutex mapMutex_;
+  std::atomic<void*> errorWords_{nullptr};  // hipHostMalloc
+  void* errorWordsDev_ = nullptr;  // ... as the device addresses it
+  void ensureErrorWords();
   uint64_t barrierGen_ = 0;
+  int sharing_ = -1;  // agreeOnSharing(): not asked yet, 0, 1
 };
 
 }  // namespace gloo_amd

@@ -28,6 +28,19 @@
 //     system ROCm) and by address on HIP 7.0.51831 (the runtime PyTorch
 //     2.10+rocm7.0 bundles and loads in place of the system one), which
 //     crashes on the value (r5j_vmm_torch_*): chosen by runtime version.
+// Fallback.  Systems exist whose runtime exports a dma-buf and refuses every
+// import of one in ANOTHER process (hipMemImportFromShareableHandle: invalid
+// argument, on HIP 7.0 and 7.2; an import in the exporting process succeeds,
+// so a process cannot find it out alone).  The ranks of a context that spans
+// processes therefore try it once (agreeOnSharing: every rank exports one
+// granule, a peer process imports it, the verdicts are exchanged), and a
+// process that has seen a refusal shares through hipIpc handles from then
+// on: slabs are plain allocations (uncached where peers write them) whose
+// handle the owner's server hands out in place of an fd, pooled by size
+// class, opened once and never freed in the same way, but below 2 GiB each
+// (an open of 2 GiB or more hangs), and no caller's allocation is exported
+// (exportRange refuses; the transport lands in a slab).  A handle names an
+// address, which is why only memory that is never freed is shared this way.
 // Rounds 3-4 shared hipMalloc blocks through hipIpc handles instead; that
 // pool (trims, retired address ranges, parked blocks, a 1.75 GiB cap) is
 // gone (DESIGN.md "Cross-process memory").
@@ -45,6 +58,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
 
 namespace gloo_amd {
 namespace ipc {
@@ -58,9 +74,10 @@ struct Slab {
   int device = -1;
   bool fine = false;     // uncached memory: what a peer writes is never behind a stale line
   uint64_t id = 0;       // names the slab to peers
-  hipMemGenericAllocationHandle_t handle = nullptr;
-  int fd = -1;           // the exported dma-buf
+  hipMemGenericAllocationHandle_t handle = nullptr;  // VMM block (nullptr: a plain allocation shared by `ipc`)
+  int fd = -1;           // its exported dma-buf
   uint64_t devices = 0;  // bit d: device d of this process may access the mapping
+  hipIpcMemHandle_t ipc; // what a peer process opens
 };
 
 // What a peer publishes about one of its slabs.
@@ -120,9 +137,20 @@ struct RangeImport {
 RangeImport importRange(const Remote& r, uint64_t offset, size_t bytes, int device);
 void unimportRange(RangeImport* m);
 
+// Whether the pool shares dma-bufs (any size) or, after a peer process's
+// import was refused, hipIpc handles (below 2 GiB).
+bool dmabufSharing();
+// Collective over the ranks of a context that spans processes, before its
+// first slab: tries a dma-buf import between processes and settles
+// dmabufSharing() for this process (a refusal is final).  `exchange(tag,
+// mine)` is the context's allgather.  Returns dmabufSharing().
+using Exchange = std::function<std::vector<std::vector<char>>(const std::string&, const std::vector<char>&)>;
+bool agreeOnSharing(int rank, int size, int device, const Exchange& exchange);
+
 struct Stats {
   size_t slabs = 0, slabBytes = 0, free = 0, imports = 0, opens = 0;
   size_t dropped = 0;  // mappings of exited processes (their pid reused) unmapped
+  bool anySize = false;  // dmabufSharing(): slabs of any size (false: hipIpc handles, below 2 GiB)
 };
 Stats stats();
 

@@ -10,8 +10,9 @@
 //           ONE system-scope acquire after the match; give up after
 //           `timeoutTicks` of the 100 MHz realtime counter and set *err (the
 //           host raises IoException).
-// Flags are 64-bit counters in the node's shared control block, registered
-// with hipHostRegister so every GPU of every rank can address them.
+// Flags are 64-bit counters in a receiver's device mailbox, or in the node's
+// shared control block, which is registered with hipHostRegister on the
+// first device-side use (context.h) so every GPU of every rank can address it.
 //
 // Replayable sequence numbers: every value a kernel waits for or writes is
 //   Seq{base, perRun}.value(epoch) = base + epoch * perRun   (mod 2^64)

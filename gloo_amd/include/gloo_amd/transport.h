@@ -127,8 +127,10 @@ class Device {
   };
   static_assert(sizeof(MsgRecord) == 64, "one line per record");
   Channel& channel(int src, int dst, int idx);
-  // The channel's arrival counter as a device kernel addresses it (the
-  // transport block registered with HIP on first use).
+  // The channel's arrival counter as a device kernel addresses it (a block
+  // shared between processes is registered with HIP on first use); nullptr
+  // where the system cannot pin memory a process already has mapped: the
+  // sender then publishes arrivals from a stream-ordered host function.
   uint64_t* channelDevicePtr(int src, int dst, int idx);
   // The record arrival `k` of channel (src -> dst, idx) uses.
   MsgRecord& msgRecord(int src, int dst, int idx, uint64_t k);
@@ -164,7 +166,10 @@ class Device {
   std::vector<std::vector<bool>> channelUsed_;  // [src][idx], this rank as receiver
   void* block_ = nullptr;
   size_t blockBytes_ = 0;
-  void* blockDev_ = nullptr;  // block_ as registered with HIP (channelDevicePtr)
+  void* blockDev_ = nullptr;  // block_ as the GPU addresses it (channelDevicePtr)
+  bool blockPinned_ = true;   // every rank is of this process: block_ is pinned memory they share by address
+  std::shared_ptr<void> blockHold_;
+  bool blockUnpinnable_ = false;  // the system refused to register the shared segment
 };
 
 class Buffer {

@@ -753,8 +753,16 @@ int gloo_hip_algorithm_run(gloo_hip_algorithm_t algo);
  * [3] = peer slabs mapped, [4] = imports made (a peer slab is mapped once and
  * kept). */
 int gloo_hip_ipc_stats(uint64_t* out5);
-/* The same, up to 6 words: + mappings of exited peers (their pid reused)
- * dropped. */
+/* Collective over the context's ranks (the library makes it by itself before
+ * a context that spans processes shares memory): they try a dma-buf import
+ * between their processes.  *any_size = 1: slabs of any size; 0: the system
+ * refuses such imports and memory is shared through hipIpc handles, below
+ * 2 GiB.  No reference counterpart. */
+int gloo_hip_context_agree_on_sharing(gloo_hip_context_t ctx, int* any_size);
+/* The same, up to 7 words: + mappings of exited peers (their pid reused)
+ * dropped, + 1 while this process shares slabs of any size (dma-bufs), 0 once
+ * a peer process's import of one was refused (hipIpc handles from then on,
+ * below 2 GiB). */
 int gloo_hip_ipc_stats_ex(uint64_t* out, size_t n);
 int gloo_hip_algorithm_destroy(gloo_hip_algorithm_t algo);
 /* Host seconds the last run() spent blocked waiting for peers. */

@@ -284,6 +284,10 @@ def run_big_arena(P, algo, n, env=None):
     ("halving_doubling", 1_000_000_000, {"GLOO_AMD_MESH": "0"}),
 ], ids=["hd_mesh_2gib", "hd_mesh_1.9gib", "ring_mesh_2gib", "hd_reference_route_2gib", "hd_reference_route_2gb_message"])
 def test_ipc_arena_of_2gib_and_more(torch, algo, n, env):
+    from sharing_probe import processes_share_any_size
+    if not processes_share_any_size():
+        pytest.skip("this system's runtime refuses to import a dma-buf (hipMemImportFromShareableHandle): processes "
+                    "share memory through hipIpc handles only, which cannot open 2 GiB or more")
     outs = run_big_arena(2, algo, n, env)
     for o in outs:
         assert o["bad"] == [0, 0], o

@@ -118,7 +118,10 @@ def test_watchdog_fire_exits_nonzero(gpu):
     """A hung N>1 section must show in the driver's record: the watchdog
     prints the line with the section marked timed out, then the job fails."""
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--full", "--config3-only", "--no-cpu", "--no-host-staged", "--watchdog-seconds", "0.5"]
+           "--full", "--config3-only", "--no-cpu", "--no-host-staged", "--watchdog-seconds", "0.5",
+           # (the section's overall limit too: where set-up is quick no single
+           # step of it pauses for half a second, and the section still runs for seconds)
+           "--watchdog-total-seconds", "0.5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=ROOT)
     assert r.returncode != 0, r.stdout[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

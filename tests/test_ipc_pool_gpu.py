@@ -36,6 +36,7 @@ for n in sizes:
     buf = ((i7 + rank) % 4096).float()
     want = ((i7 % 4096) + ((i7 + 1) % 4096)).float()
     del i7
+    torch.cuda.synchronize()  # buf is complete before the executor's own stream reads it (as below)
     a = gloo_amd.Algorithm(ctx, "halving_doubling", "sum", "f32", [buf.data_ptr()], n)
     ok = []
     for it in range(2):

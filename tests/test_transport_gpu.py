@@ -336,5 +336,10 @@ def test_transport_device_buffer_reallocated_at_same_address(tmp_path):
 
 @pytest.mark.timeout(150)
 def test_transport_receive_buffer_of_2p5gib_across_processes(tmp_path):
+    pytest.importorskip("torch")
+    from sharing_probe import processes_share_any_size
+    if not processes_share_any_size():
+        pytest.skip("this system's runtime refuses to import a dma-buf (hipMemImportFromShareableHandle): processes "
+                    "share memory through hipIpc handles only, which cannot open 2 GiB or more")
     res = run_transport_case(tmp_path, "big_alloc")
     assert res[1]["bad"] == [0, 0, 0], res
