@@ -23,7 +23,9 @@ LIB_PATH = os.environ.get("GLOO_AMD_LIB") or os.path.join(_HERE, "libgloo_amd.so
 
 class ReductionType(enum.IntEnum):
     """gloo::ReductionType (gloo/algorithm.h:49-57), extended by the bitwise
-    ops of PyTorch's ReduceOp (BAND / BOR / BXOR; integer dtypes only)."""
+    ops of PyTorch's ReduceOp (BAND / BOR / BXOR; integer dtypes only) and by
+    SUM_WIDE (f16 / bf16 / f8e4m3 / f8e5m2 only): SUM carried in f32 and rounded
+    once per k-source pass, include/gloo_amd.h "Wide sum"."""
     SUM = 1
     PRODUCT = 2
     MAX = 3
@@ -31,6 +33,7 @@ class ReductionType(enum.IntEnum):
     BAND = 5
     BOR = 6
     BXOR = 7
+    SUM_WIDE = 257  # GLOO_HIP_SUM | GLOO_HIP_WIDE (0x100)
 
 
 class DType(enum.IntEnum):
@@ -54,6 +57,8 @@ DTYPE_NAMES = {"i8": DType.I8, "u8": DType.U8, "i32": DType.I32, "u32": DType.U3
 OP_NAMES = {"sum": ReductionType.SUM, "product": ReductionType.PRODUCT,
             "max": ReductionType.MAX, "min": ReductionType.MIN,
             "band": ReductionType.BAND, "bor": ReductionType.BOR, "bxor": ReductionType.BXOR}
+# the ops that are a modifier bit on one of the above (include/gloo_amd.h GLOO_HIP_WIDE); _as_op takes both tables
+MODIFIED_OP_NAMES = {"sum_wide": ReductionType.SUM_WIDE}
 
 EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_dtype_size", "gloo_hip_last_error", "gloo_hip_version",
@@ -129,7 +134,9 @@ def _check(rc):
 
 
 def _as_op(op):
-    return int(OP_NAMES[op]) if isinstance(op, str) else int(op)  # ints: built-in or registered (>= 1000)
+    if isinstance(op, str):
+        return int(MODIFIED_OP_NAMES[op] if op in MODIFIED_OP_NAMES else OP_NAMES[op])
+    return int(op)  # ints: built-in or registered (>= 1000)
 
 
 def _as_dtype(dtype):
@@ -142,7 +149,8 @@ def dtype_size(dtype):
 
 def op_supported(op, dtype):
     """gloo_hip_op_supported: do the kernels implement `op` on `dtype`?  (The
-    bitwise ops take the integer dtypes only.)  Never touches the GPU."""
+    bitwise ops take the integer dtypes only, the wide sum f16 / bf16 / f8e4m3 /
+    f8e5m2 only.)  Never touches the GPU."""
     return bool(lib.gloo_hip_op_supported(_as_op(op), _as_dtype(dtype)))
 
 
@@ -351,6 +359,7 @@ ReductionFunction.min = ReductionFunction(ReductionType.MIN)
 ReductionFunction.band = ReductionFunction(ReductionType.BAND)
 ReductionFunction.bor = ReductionFunction(ReductionType.BOR)
 ReductionFunction.bxor = ReductionFunction(ReductionType.BXOR)
+ReductionFunction.sum_wide = ReductionFunction(ReductionType.SUM_WIDE)
 
 
 # ---- contexts and algorithms (GPU allreduce / reduce-scatter drop-ins) -----

@@ -507,6 +507,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     void* user;
     custom_ = customOp(op_, &fn, &user);
     GLOO_AMD_ENFORCE(custom_ || isBuiltinOp(op_, dtype_), "unknown op ", op_, " for dtype ", dtype_);
+    wide_ = op_ == GLOO_HIP_SUM_WIDE;
   }
   GLOO_AMD_ENFORCE(!ptrs_.empty(), "need at least one pointer");
   GLOO_AMD_ENFORCE(!isAlltoall(algo_) || (inputs_.size() == 1 && ptrs_.size() == 1),
@@ -754,7 +755,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     const char* im = std::getenv("GLOO_AMD_INTERP");
     const char* gm = std::getenv("GLOO_AMD_GRAPH");
     interpMode_ = deviceSignal_ && !(im && std::string(im) == "0") && !(gm && std::string(gm) == "1") &&
-                  interpBytes() > 0 && !custom_;
+                  interpBytes() > 0 && !custom_ && !wide_;
   }
   // The sliced interpreter's slices spin until their peer slices run, so
   // every launch of the ranks on one GPU must be resident at once.  Measured

@@ -1195,7 +1195,9 @@ void PlanExecutor::enqueue(uint64_t r, bool graph) {
     // the reference's association and operand order.  The wait stays a
     // kernel of its own: a grid that spins while it holds the GPU could
     // starve the sender where ranks share one.
-    if (fuseLocal && foldsWithReceive(steps, i, ptrs_.size())) {
+    // (Not the wide sum: the pass would carry the inbox in the accumulator
+    // too, where the plan's REDUCE rounds first.)
+    if (fuseLocal && !wide_ && foldsWithReceive(steps, i, ptrs_.size())) {
       const Step &w = steps[i + 1], &rd = steps[i + 2];
       GLOO_AMD_HIP_CHECK(launchWait(waitFlag(w.peer, w.slot), seqOf(i + 1, r, graph), epoch, timeoutTicks,
                                     ctx_->errorWordDevicePtr(me), stream_));

@@ -717,9 +717,163 @@ __device__ __forceinline__ void fold_tile(const SrcList& srcs, int k, size_t hea
   }
 }
 
+// ---------------------------------------------------------------------------
+// Wide sum (GLOO_HIP_SUM_WIDE; F16, BF16, F8E4M3, F8E5M2; k >= 3 sources): the
+// pass carries every element in an f32 accumulator, a = f32(s_0); a = a +
+// f32(s_j) in list order, and narrows ONCE after the last source (include/
+// gloo_amd.h "Wide sum").  fold_tile's twin: the tile split, the per-source
+// misalignment in soffset and the "two tiles in flight" load order are the
+// same; what differs is that the accumulator is UNROLL x (16 / sizeof(S)) f32
+// VGPRs per lane instead of UNROLL packets, that source j + 1's packets are
+// requested before source j's are widened and added, and that the fold mode
+// does not exist (f32 addition commutes, and the tree is evaluated as this
+// left fold: one streaming accumulator set instead of a tree of f32 tiles).
+//
+// The adds are single v_add_f32 (kernels built with packed f32 arithmetic off,
+// GLOO_WIDE_KERNEL): each is one IEEE binary32 add, denormals kept, nothing
+// to contract.  Widening is the packed form of each format: word-selected
+// v_cvt_pk_f32_fp8 / _bf8 (two elements each), shift / mask of the dword for
+// bf16, the two halves of the dword for f16.
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GLOO_WIDE_KERNEL __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GLOO_WIDE_KERNEL
+#endif
+
+template <class Tr>
+constexpr bool kHasWide = std::is_same<Tr, TrF16>::value || std::is_same<Tr, TrBF16>::value ||
+                          std::is_same<Tr, TrF8E4M3>::value || std::is_same<Tr, TrF8E5M2>::value;
+
+// The contract's single narrowing: the dtype's own rule, with the canonical
+// 0x7E00 for an fp16 NaN (TrF16's operand-payload rule belongs to a
+// two-operand op).
+template <class Tr>
+__device__ __forceinline__ typename Tr::Storage wide_narrow(float a) {
+  if constexpr (std::is_same<Tr, TrF16>::value) return a != a ? (uint16_t)0x7E00u : TrF16::narrow(a);
+  else return Tr::narrow(a);
+}
+
+// One packet's elements widened into (FIRST) or added onto kV accumulators.
+template <class Tr, bool FIRST>
+__device__ __forceinline__ void wide_add_packet(u32x4 p, float (&a)[16 / sizeof(typename Tr::Storage)]) {
+  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    if constexpr (sizeof(typename Tr::Storage) == 1) {
+      const f32x2 lo = Tr::template widen2<false>(w[d]), hi = Tr::template widen2<true>(w[d]);
+      const float v[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+      for (int e = 0; e < 4; e++) a[4 * d + e] = FIRST ? v[e] : a[4 * d + e] + v[e];
+    } else {
+      float lo, hi;
+      if constexpr (std::is_same<Tr, TrBF16>::value) {
+        lo = __builtin_bit_cast(float, w[d] << 16);
+        hi = __builtin_bit_cast(float, w[d] & 0xFFFF0000u);
+      } else {
+        const h2 h = __builtin_bit_cast(h2, w[d]);
+        lo = (float)h.x;
+        hi = (float)h.y;
+      }
+      a[2 * d] = FIRST ? lo : a[2 * d] + lo;
+      a[2 * d + 1] = FIRST ? hi : a[2 * d + 1] + hi;
+    }
+  }
+}
+
+// kV accumulators narrowed once into a packet.  FP8: packed narrows plus the
+// `special` detect of the two-operand path; a packet holding a sum the
+// convert's byte does not stand for is redone element by element.  f16: the
+// converts, then the packet's NaNs (found as f16_pk_packet finds them) made
+// canonical.  bf16: TrBF16::narrow carries its NaN select.
+template <class Tr>
+__device__ __forceinline__ u32x4 wide_narrow_packet(const float (&a)[16 / sizeof(typename Tr::Storage)]) {
+  uint32_t w[4];
+  if constexpr (sizeof(typename Tr::Storage) == 1) {
+    bool special = false;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+      special = special || Tr::special(a[4 * d]) || Tr::special(a[4 * d + 1]) || Tr::special(a[4 * d + 2]) ||
+                Tr::special(a[4 * d + 3]);
+      w[d] = Tr::template narrow2<true>(a[4 * d + 2], a[4 * d + 3], Tr::template narrow2<false>(a[4 * d], a[4 * d + 1], 0));
+    }
+    if (__builtin_expect(special, 0)) {
+#pragma unroll
+      for (int d = 0; d < 4; d++)
+        w[d] = (uint32_t)Tr::narrow(a[4 * d]) | (uint32_t)Tr::narrow(a[4 * d + 1]) << 8 |
+               (uint32_t)Tr::narrow(a[4 * d + 2]) << 16 | (uint32_t)Tr::narrow(a[4 * d + 3]) << 24;
+    }
+  } else {
+#pragma unroll
+    for (int d = 0; d < 4; d++) w[d] = (uint32_t)Tr::narrow(a[2 * d]) | (uint32_t)Tr::narrow(a[2 * d + 1]) << 16;
+    if constexpr (std::is_same<Tr, TrF16>::value) {
+      const uint32_t nan = f16_nan_bits(w[0]) | f16_nan_bits(w[1]) | f16_nan_bits(w[2]) | f16_nan_bits(w[3]);
+      if (__builtin_expect((nan & 0x80008000u) != 0, 0)) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) w[d] = bsel(f16_nan_mask(w[d]), 0x7E007E00u, w[d]);
+      }
+    }
+  }
+  return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// One element of a wide fold (block 0's head / tail).
+template <class Tr>
+__device__ __forceinline__ typename Tr::Storage wide_elem(const SrcList& srcs, int k, size_t i) {
+  using S = typename Tr::Storage;
+  float a = Tr::widen(static_cast<const S*>(srcs.p[0])[i]);
+  for (int j = 1; j < k; j++) a = a + Tr::widen(static_cast<const S*>(srcs.p[j])[i]);
+  return wide_narrow<Tr>(a);
+}
+
+// One vector tile of a wide fold (k >= 2), into acc as fold_tile leaves it.
+template <class Tr, int UNROLL, int BLOCK>
+__device__ __forceinline__ void wide_tile(const SrcList& srcs, int k, size_t head, size_t base, uint32_t bytes,
+                                          u32x4 (&acc)[UNROLL]) {
+  using S = typename Tr::Storage;
+  constexpr int kV = 16 / sizeof(S);
+  const uint32_t lane_off = threadIdx.x * 16u;
+  float a[UNROLL][kV];
+  u32x4 cur[UNROLL], nxt[UNROLL];
+  auto request = [&](int j, u32x4(&v)[UNROLL]) {
+    const Src sj = src_of(static_cast<const S*>(srcs.p[j]) + head);
+    const auto rj = make_rsrc(sj.base + base, bytes + sj.mis);
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) v[u] = bload<kAuxNT>(rj, lane_off + u * BLOCK * 16, sj.mis);
+  };
+  request(0, cur);
+  request(1, nxt);
+#pragma unroll
+  for (int u = 0; u < UNROLL; u++) wide_add_packet<Tr, true>(cur[u], a[u]);
+  for (int j = 1; j < k; j++) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) cur[u] = nxt[u];
+    if (j + 1 < k) request(j + 1, nxt);  // in flight while source j is widened and added
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) wide_add_packet<Tr, false>(cur[u], a[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < UNROLL; u++) acc[u] = wide_narrow_packet<Tr>(a[u]);
+}
+
+// OP's fold of one element / one tile: the wide sum's accumulator path, or
+// MODE's order of the two-operand op.
+template <class Tr, int OP, int MODE>
+__device__ __forceinline__ typename Tr::Storage fold_elem_of(const SrcList& srcs, int k, size_t i) {
+  if constexpr (OP == GLOO_HIP_SUM_WIDE) return wide_elem<Tr>(srcs, k, i);
+  else return fold_elem<Tr, OP, MODE>(srcs, k, i);
+}
 template <class Tr, int OP, int UNROLL, int BLOCK, int MODE>
-__global__ __launch_bounds__(BLOCK) void reduce_multi_vec_kernel(
-    typename Tr::Storage* dst, SrcList srcs, int k, size_t n, size_t head, uint64_t* stamp, int plain) {
+__device__ __forceinline__ void fold_tile_of(const SrcList& srcs, int k, size_t head, size_t base, uint32_t bytes,
+                                             u32x4 (&acc)[UNROLL]) {
+  if constexpr (OP == GLOO_HIP_SUM_WIDE) wide_tile<Tr, UNROLL, BLOCK>(srcs, k, head, base, bytes, acc);
+  else fold_tile<Tr, OP, UNROLL, BLOCK, MODE>(srcs, k, head, base, bytes, acc);
+}
+
+// The k-source fold's pass (the body of both kernels below).
+template <class Tr, int OP, int UNROLL, int BLOCK, int MODE>
+__device__ __forceinline__ void reduce_multi_body(typename Tr::Storage* dst, const SrcList& srcs, int k, size_t n,
+                                                  size_t head, uint64_t* stamp, int plain) {
   using S = typename Tr::Storage;
   constexpr int kV = 16 / sizeof(S);
   constexpr uint32_t kTileBytes = (uint32_t)BLOCK * UNROLL * 16;
@@ -730,7 +884,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_multi_vec_kernel(
     const size_t t = threadIdx.x;
     for (int pass = 0; pass < 2; pass++) {
       const size_t i = pass == 0 ? t : tail0 + t;
-      if ((pass == 0 && t < head) || (pass == 1 && i < n)) dst[i] = fold_elem<Tr, OP, MODE>(srcs, k, i);
+      if ((pass == 0 && t < head) || (pass == 1 && i < n)) dst[i] = fold_elem_of<Tr, OP, MODE>(srcs, k, i);
     }
   }
   const size_t body = nvec * 16;
@@ -739,7 +893,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_multi_vec_kernel(
   const uint32_t bytes = (uint32_t)((body - base) < kTileBytes ? (body - base) : kTileBytes);
   const uint32_t lane_off = threadIdx.x * 16u;
   u32x4 acc[UNROLL];
-  fold_tile<Tr, OP, UNROLL, BLOCK, MODE>(srcs, k, head, base, bytes, acc);
+  fold_tile_of<Tr, OP, UNROLL, BLOCK, MODE>(srcs, k, head, base, bytes, acc);
   const auto rd = make_rsrc(reinterpret_cast<const char*>(dst + head) + base, bytes);
   if (plain) {  // the executor's folds: the result's next reader is a send or the caller (setReducePlainStores)
 #pragma unroll
@@ -749,6 +903,18 @@ __global__ __launch_bounds__(BLOCK) void reduce_multi_vec_kernel(
     for (int u = 0; u < UNROLL; u++) bstore<kAuxNT>(rd, lane_off + u * BLOCK * 16, acc[u]);
   }
   stamp_end(stamp);
+}
+
+template <class Tr, int OP, int UNROLL, int BLOCK, int MODE>
+__global__ __launch_bounds__(BLOCK) void reduce_multi_vec_kernel(
+    typename Tr::Storage* dst, SrcList srcs, int k, size_t n, size_t head, uint64_t* stamp, int plain) {
+  reduce_multi_body<Tr, OP, UNROLL, BLOCK, MODE>(dst, srcs, k, n, head, stamp, plain);
+}
+// the same pass with the wide sum's data path (k >= 3; launch_multi_wide)
+template <class Tr, int UNROLL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) GLOO_WIDE_KERNEL void reduce_multi_wide_kernel(
+    typename Tr::Storage* dst, SrcList srcs, int k, size_t n, size_t head, uint64_t* stamp, int plain) {
+  reduce_multi_body<Tr, GLOO_HIP_SUM_WIDE, UNROLL, BLOCK, 0>(dst, srcs, k, n, head, stamp, plain);
 }
 
 // ---------------------------------------------------------------------------
@@ -1409,10 +1575,10 @@ struct FwdList {
   unsigned* ticket;                 // zero between launches; nullptr: no signals
 };
 
+// (the pass is fold_send_body, shared by the kernel and its wide-sum twin)
 template <class Tr, int OP>
-__global__ __launch_bounds__(kVecBlock) void fold_send_kernel(typename Tr::Storage* dst, SrcList srcs, int k,
-                                                              int mode, size_t n, size_t head, FwdList F,
-                                                              const uint64_t* epoch, uint64_t* stamp) {
+__device__ __forceinline__ void fold_send_body(typename Tr::Storage* dst, const SrcList& srcs, int k, int mode, size_t n,
+                                               size_t head, const FwdList& F, const uint64_t* epoch, uint64_t* stamp) {
   using S = typename Tr::Storage;
   constexpr int kV = 16 / sizeof(S);
   constexpr int UNROLL = kMultiUnroll, BLOCK = kVecBlock;
@@ -1425,9 +1591,9 @@ __global__ __launch_bounds__(kVecBlock) void fold_send_kernel(typename Tr::Stora
     for (int pass = 0; pass < 2; pass++) {
       const size_t i = pass == 0 ? t : tail0 + t;
       if ((pass == 0 && t < head) || (pass == 1 && i < n)) {
-        const S acc = mode == 2   ? fold_elem<Tr, OP, 2>(srcs, k, i)
-                      : mode == 1 ? fold_elem<Tr, OP, 1>(srcs, k, i)
-                                  : fold_elem<Tr, OP, 0>(srcs, k, i);
+        const S acc = mode == 2   ? fold_elem_of<Tr, OP, 2>(srcs, k, i)
+                      : mode == 1 ? fold_elem_of<Tr, OP, 1>(srcs, k, i)
+                                  : fold_elem_of<Tr, OP, 0>(srcs, k, i);
         dst[i] = acc;
         for (int r = 0; r < F.n; r++)
           if (F.dst[r]) reinterpret_cast<S*>(F.dst[r])[i] = acc;
@@ -1440,9 +1606,9 @@ __global__ __launch_bounds__(kVecBlock) void fold_send_kernel(typename Tr::Stora
     const uint32_t bytes = (uint32_t)((body - base) < kTileBytes ? (body - base) : kTileBytes);
     const uint32_t lane_off = threadIdx.x * 16u;
     u32x4 acc[UNROLL];
-    if (mode == 2) fold_tile<Tr, OP, UNROLL, BLOCK, 2>(srcs, k, head, base, bytes, acc);
-    else if (mode == 1) fold_tile<Tr, OP, UNROLL, BLOCK, 1>(srcs, k, head, base, bytes, acc);
-    else fold_tile<Tr, OP, UNROLL, BLOCK, 0>(srcs, k, head, base, bytes, acc);
+    if (mode == 2) fold_tile_of<Tr, OP, UNROLL, BLOCK, 2>(srcs, k, head, base, bytes, acc);
+    else if (mode == 1) fold_tile_of<Tr, OP, UNROLL, BLOCK, 1>(srcs, k, head, base, bytes, acc);
+    else fold_tile_of<Tr, OP, UNROLL, BLOCK, 0>(srcs, k, head, base, bytes, acc);
     const auto rd = make_rsrc(reinterpret_cast<const char*>(dst + head) + base, bytes);
     // plain local stores: the result stays in the Infinity Cache for its
     // next reader (`nt` measured slower per call)
@@ -1485,6 +1651,20 @@ __global__ __launch_bounds__(kVecBlock) void fold_send_kernel(typename Tr::Stora
 }
 
 template <class Tr, int OP>
+__global__ __launch_bounds__(kVecBlock) void fold_send_kernel(typename Tr::Storage* dst, SrcList srcs, int k,
+                                                              int mode, size_t n, size_t head, FwdList F,
+                                                              const uint64_t* epoch, uint64_t* stamp) {
+  fold_send_body<Tr, OP>(dst, srcs, k, mode, n, head, F, epoch, stamp);
+}
+// the wide sum's fold + forward (k >= 3): no mode, the same stores and completion
+template <class Tr>
+__global__ __launch_bounds__(kVecBlock) GLOO_WIDE_KERNEL void fold_send_wide_kernel(
+    typename Tr::Storage* dst, SrcList srcs, int k, size_t n, size_t head, FwdList F, const uint64_t* epoch,
+    uint64_t* stamp) {
+  fold_send_body<Tr, GLOO_HIP_SUM_WIDE>(dst, srcs, k, 0, n, head, F, epoch, stamp);
+}
+
+template <class Tr, int OP>
 int launch_fold_send(void* dst, const SrcList& list, int k, int mode, size_t n, const FwdList& F,
                      const uint64_t* epoch, hipStream_t s) {
   using S = typename Tr::Storage;
@@ -1494,15 +1674,26 @@ int launch_fold_send(void* dst, const SrcList& list, int k, int mode, size_t n, 
   const size_t nvec = (n - head) / kV;
   size_t grid = ceil_div(nvec, (size_t)kVecBlock * kMultiUnroll);
   if (grid == 0) grid = 1;
-  fold_send_kernel<Tr, OP><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(static_cast<S*>(dst), list, k, mode, n,
-                                                                          head, F, epoch, t_stamp);
-  return check_launch("fold_send_kernel");
+  if constexpr (OP == GLOO_HIP_SUM_WIDE) {
+    fold_send_wide_kernel<Tr><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(static_cast<S*>(dst), list, k, n, head, F,
+                                                                             epoch, t_stamp);
+    return check_launch("fold_send_wide_kernel");
+  } else {
+    fold_send_kernel<Tr, OP><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(static_cast<S*>(dst), list, k, mode, n,
+                                                                            head, F, epoch, t_stamp);
+    return check_launch("fold_send_kernel");
+  }
 }
 
 template <class Tr>
 int by_op_fold_send(int op, void* dst, const SrcList& list, int k, int mode, size_t n, const FwdList& F,
                     const uint64_t* epoch, hipStream_t s) {
   switch (op) {
+    case GLOO_HIP_SUM_WIDE:  // a pass of k >= 3 sources is the wide kernel; k <= 2 IS SUM
+      if constexpr (kHasWide<Tr>) {
+        if (k >= 3) return launch_fold_send<Tr, GLOO_HIP_SUM_WIDE>(dst, list, k, 0, n, F, epoch, s);
+      }
+      return launch_fold_send<Tr, GLOO_HIP_SUM>(dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_SUM: return launch_fold_send<Tr, GLOO_HIP_SUM>(dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_PRODUCT: return launch_fold_send<Tr, GLOO_HIP_PRODUCT>(dst, list, k, mode, n, F, epoch, s);
     case GLOO_HIP_MAX: return launch_fold_send<Tr, GLOO_HIP_MAX>(dst, list, k, mode, n, F, epoch, s);
@@ -1599,9 +1790,15 @@ int launch_multi(void* dst, const void* const* srcs, int k, size_t n, hipStream_
   const size_t nvec = (n - head) / kV;
   size_t grid = ceil_div(nvec, (size_t)kVecBlock * kMultiUnroll);
   if (grid == 0) grid = 1;
-  reduce_multi_vec_kernel<Tr, OP, kMultiUnroll, kVecBlock, MODE><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(
-      static_cast<S*>(dst), list, k, n, head, t_stamp, t_plainStores ? 1 : 0);
-  return check_launch("reduce_multi_vec_kernel");
+  if constexpr (OP == GLOO_HIP_SUM_WIDE) {
+    reduce_multi_wide_kernel<Tr, kMultiUnroll, kVecBlock><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(
+        static_cast<S*>(dst), list, k, n, head, t_stamp, t_plainStores ? 1 : 0);
+    return check_launch("reduce_multi_wide_kernel");
+  } else {
+    reduce_multi_vec_kernel<Tr, OP, kMultiUnroll, kVecBlock, MODE><<<dim3((unsigned)grid), dim3(kVecBlock), 0, s>>>(
+        static_cast<S*>(dst), list, k, n, head, t_stamp, t_plainStores ? 1 : 0);
+    return check_launch("reduce_multi_vec_kernel");
+  }
 }
 
 template <class Tr>
@@ -1621,6 +1818,11 @@ int by_op3(int op, void* c, const void* a, const void* b, size_t n, hipStream_t 
 template <class Tr, int MODE = 0>
 int by_op_multi(int op, void* d, const void* const* srcs, int k, size_t n, hipStream_t s) {
   switch (op) {
+    case GLOO_HIP_SUM_WIDE:  // the mode is no association for it; k <= 2 IS SUM
+      if constexpr (kHasWide<Tr>) {
+        if (k >= 3) return launch_multi<Tr, GLOO_HIP_SUM_WIDE, 0>(d, srcs, k, n, s);
+      }
+      return launch_multi<Tr, GLOO_HIP_SUM, MODE>(d, srcs, k, n, s);
     case GLOO_HIP_SUM: return launch_multi<Tr, GLOO_HIP_SUM, MODE>(d, srcs, k, n, s);
     case GLOO_HIP_PRODUCT: return launch_multi<Tr, GLOO_HIP_PRODUCT, MODE>(d, srcs, k, n, s);
     case GLOO_HIP_MAX: return launch_multi<Tr, GLOO_HIP_MAX, MODE>(d, srcs, k, n, s);
@@ -1635,6 +1837,14 @@ int by_op_multi(int op, void* d, const void* const* srcs, int k, size_t n, hipSt
 
 inline bool isBitwiseOp(int op) { return op >= GLOO_HIP_BAND && op <= GLOO_HIP_BXOR; }
 inline bool isIntegerDtype(int dtype) { return dtype >= GLOO_HIP_I8 && dtype <= GLOO_HIP_U64; }
+// the wide sum's dtypes (kHasWide)
+inline bool isNarrowFloatDtype(int dtype) {
+  return dtype == GLOO_HIP_F16 || dtype == GLOO_HIP_BF16 || dtype == GLOO_HIP_F8E4M3 || dtype == GLOO_HIP_F8E5M2;
+}
+// The op whose kernels a two-operand pass runs: one add has nothing to widen
+// over, so SUM_WIDE IS SUM there and no two-operand kernel is instantiated for
+// it (as bitwiseKernelDtype spares the signed bitwise instances).
+inline int twoOperandOp(int op) { return op == GLOO_HIP_SUM_WIDE ? GLOO_HIP_SUM : op; }
 
 // The dtype whose kernels run `op`: a bitwise op on a signed integer dtype runs
 // the unsigned twin's (kHasBitwise); every other pair is left as it is.
@@ -1650,6 +1860,7 @@ inline int bitwiseKernelDtype(int op, int dtype) {
 
 int dispatch3(int op, int dtype, void* c, const void* a, const void* b, size_t n,
               hipStream_t s) {
+  op = twoOperandOp(op);
   switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: return by_op3<TrI8>(op, c, a, b, n, s);
     case GLOO_HIP_U8: return by_op3<TrU8>(op, c, a, b, n, s);
@@ -1800,15 +2011,19 @@ std::vector<CustomEntry>& customOps() {
 bool isBuiltinOp(int op, int dtype) {
   if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return false;
   if (op >= GLOO_HIP_SUM && op <= GLOO_HIP_MIN) return true;
+  if (op == GLOO_HIP_SUM_WIDE) return isNarrowFloatDtype(dtype);
   return isBitwiseOp(op) && isIntegerDtype(dtype);
 }
 
 int checkBitwiseDtype(int op, int dtype) {
-  if (!isBitwiseOp(op) || dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES || isIntegerDtype(dtype)) return GLOO_HIP_OK;
-  static const char* const kOps[] = {"band", "bor", "bxor"};
   static const char* const kDtypes[GLOO_HIP_NUM_DTYPES] = {"i8",  "u8",  "i32",  "u32", "i64",
                                                           "u64", "f16", "bf16", "f32", "f64",
                                                           "f8e4m3", "f8e5m2"};
+  if (op == GLOO_HIP_SUM_WIDE && dtype >= 0 && dtype < GLOO_HIP_NUM_DTYPES && !isNarrowFloatDtype(dtype))
+    return setError(GLOO_HIP_EINVAL_OP, std::string("reduction op sum_wide is not defined for dtype ") + kDtypes[dtype] +
+                                            " (the wide sum takes f16, bf16, f8e4m3 and f8e5m2)");
+  if (!isBitwiseOp(op) || dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES || isIntegerDtype(dtype)) return GLOO_HIP_OK;
+  static const char* const kOps[] = {"band", "bor", "bxor"};
   return setError(GLOO_HIP_EINVAL_OP, std::string("reduction op ") + kOps[op - GLOO_HIP_BAND] +
                                           " is not defined for dtype " + kDtypes[dtype] +
                                           " (the bitwise ops take the integer dtypes)");
@@ -1851,13 +2066,15 @@ int customFold(gloo_hip_custom_fn fn, void* user, int dtype, void* dst, const vo
 int launchFold(int op, int dtype, void* dst, const void* const* srcs, int k, size_t n, int mode,
                hipStream_t s) {
   if (k < 1 || k > GLOO_HIP_MAX_SRCS) return set_error(GLOO_HIP_EINVAL_ARG, "source count out of range");
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
   gloo_hip_custom_fn cfn;
   void* cuser;
   if (customOp(op, &cfn, &cuser)) {
     if (n == 0) return GLOO_HIP_OK;
     return customFold(cfn, cuser, dtype, dst, srcs, k, n, mode, s);
   }
-  if (mode == 2 && (k & (k - 1))) return set_error(GLOO_HIP_EINVAL_ARG, "tree fold needs a power-of-two count");
+  if (mode == 2 && (k & (k - 1)) && op != GLOO_HIP_SUM_WIDE)  // (no association for the wide sum: mode ignored)
+    return set_error(GLOO_HIP_EINVAL_ARG, "tree fold needs a power-of-two count");
   if (n == 0) return GLOO_HIP_OK;
   switch (mode) {
     case 0: return dispatch_multi<0>(op, dtype, dst, srcs, k, n, s);
@@ -1871,7 +2088,8 @@ int launchFoldSend(int op, int dtype, void* dst, const void* const* srcs, int k,
                    const FwdDesc* fwd, int nf, unsigned* ticket, const uint64_t* epoch, hipStream_t s) {
   if (k < 1 || k > GLOO_HIP_MAX_SRCS) return set_error(GLOO_HIP_EINVAL_ARG, "source count out of range");
   if (nf < 1 || nf > kMaxCopyEntries) return set_error(GLOO_HIP_EINVAL_ARG, "forward count out of range");
-  if (mode < 0 || mode > 2 || (mode == 2 && (k & (k - 1))))
+  if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+  if (mode < 0 || mode > 2 || (mode == 2 && (k & (k - 1)) && op != GLOO_HIP_SUM_WIDE))
     return set_error(GLOO_HIP_EINVAL_ARG, "bad fold mode for fold+forward");
   const size_t es = gloo_hip_dtype_size(dtype);
   if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
@@ -1940,6 +2158,7 @@ int launchFusedSmall(int op, int dtype, void* dst, const void* src, size_t n, co
                      Seq waitTarget, uint64_t timeoutTicks, uint32_t* err, uint64_t* sigFlag, Seq sigValue,
                      const uint64_t* epoch, hipStream_t s) {
   int rc;
+  op = twoOperandOp(op);
   switch (bitwiseKernelDtype(op, dtype)) {
     case GLOO_HIP_I8: rc = launch_fused<TrI8>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
     case GLOO_HIP_U8: rc = launch_fused<TrU8>(op, dst, src, n, waitFlag, waitTarget, timeoutTicks, err, sigFlag, sigValue, epoch, s); break;
@@ -1997,6 +2216,7 @@ int gloo_hip_reduce3(int op, int dtype, void* c, const void* a, const void* b, s
   void* cuser = nullptr;
   const bool custom = customOp(op, &cfn, &cuser);
   if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
+  op = twoOperandOp(op);
   if (n == 0) {
     if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_BXOR)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
     if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
@@ -2063,7 +2283,8 @@ int gloo_hip_fold_kernel(int op, int dtype, void* dst, const void* const* srcs, 
   if (k < 1 || k > GLOO_HIP_MAX_SRCS) return set_error(GLOO_HIP_EINVAL_ARG, "source count out of range");
   if (nfwd < 0 || nfwd > gloo_amd::kMaxCopyEntries) return set_error(GLOO_HIP_EINVAL_ARG, "forward count out of range");
   if (mode < 0 || mode > 2) return set_error(GLOO_HIP_EINVAL_ARG, "unknown fold mode");
-  if (mode == 2 && (k & (k - 1))) return set_error(GLOO_HIP_EINVAL_ARG, "tree fold needs a power-of-two count");
+  if (mode == 2 && (k & (k - 1)) && op != GLOO_HIP_SUM_WIDE)  // (no association for the wide sum: mode ignored)
+    return set_error(GLOO_HIP_EINVAL_ARG, "tree fold needs a power-of-two count");
   const size_t es = gloo_hip_dtype_size(dtype);
   if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
@@ -2131,6 +2352,8 @@ int gloo_hip_interp_kernel(int op, int dtype, const gloo_hip_interp_step_t* step
   if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
   if (!isBuiltinOp(op, dtype)) return set_error(GLOO_HIP_EINVAL_OP, "the interpreter takes a built-in op");
+  if (op == GLOO_HIP_SUM_WIDE)  // its folds round per two-operand step; the executor keeps the op off it too
+    return set_error(GLOO_HIP_EINVAL_OP, "the interpreter does not run sum_wide (a plan with it is replayed or enqueued)");
   std::vector<InterpStep> v((size_t)nsteps);
   for (int i = 0; i < nsteps; i++) {
     const gloo_hip_interp_step_t& s = steps[i];
@@ -2250,7 +2473,8 @@ int gloo_hip_reduce_multi(int op, int dtype, void* dst, const void* const* srcs,
   void* cuser = nullptr;
   const bool custom = customOp(op, &cfn, &cuser);
   if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
-  if (!custom && (op < GLOO_HIP_SUM || op > GLOO_HIP_BXOR)) return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
+  if (!custom && op != GLOO_HIP_SUM_WIDE && (op < GLOO_HIP_SUM || op > GLOO_HIP_BXOR))
+    return set_error(GLOO_HIP_EINVAL_OP, "unknown reduction op");
   if (dtype < 0 || dtype >= GLOO_HIP_NUM_DTYPES) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   if (n == 0) return GLOO_HIP_OK;
   if (!dst || !srcs) return set_error(GLOO_HIP_EINVAL_PTR, "null buffer pointer");

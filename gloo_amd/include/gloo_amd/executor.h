@@ -189,6 +189,11 @@ class PlanExecutor {
   std::shared_ptr<Context> ctx_;
   int algo_, op_, dtype_;
   bool custom_ = false;  // op_ is a registered custom reduction (gloo_hip_register_op)
+  // op_ is GLOO_HIP_SUM_WIDE: every FOLD / LOCAL_REDUCE is one wide pass and
+  // every REDUCE is SUM, so nothing may merge or split the plan's arithmetic
+  // passes: no interpreter (its folds round per step) and no local fold +
+  // receive-reduce pass; the bits are then the plan's in every launch mode
+  bool wide_ = false;
   int planAlgo_;  // the plan executed (RING_CHUNKED may run as RING_CHUNKED_MESH)
   size_t es_;
   std::vector<void*> ptrs_;     // outputs (the reference's ptrs_ / out)

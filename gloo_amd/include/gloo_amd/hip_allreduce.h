@@ -65,7 +65,8 @@ template <> struct DType<float8_e4m3fn> { static constexpr int value = GLOO_HIP_
 template <> struct DType<float8_e5m2> { static constexpr int value = GLOO_HIP_F8E5M2; };
 
 // gloo::ReductionType values (gloo/algorithm.h:49-57), extended by the
-// bitwise ops of the integer types (include/gloo_amd.h gloo_hip_op_t).
+// bitwise ops of the integer types and the wide sum of the 16-bit and 8-bit
+// floating types (include/gloo_amd.h gloo_hip_op_t).
 enum ReductionType {
   SUM = GLOO_HIP_SUM,
   PRODUCT = GLOO_HIP_PRODUCT,
@@ -74,6 +75,7 @@ enum ReductionType {
   BAND = GLOO_HIP_BAND,
   BOR = GLOO_HIP_BOR,
   BXOR = GLOO_HIP_BXOR,
+  SUM_WIDE = GLOO_HIP_SUM_WIDE,
 };
 
 // Device reduction function: call() enqueues dst = dst op src on `stream`
@@ -91,6 +93,10 @@ class HipReductionFunction {
   static const HipReductionFunction<T>* band;
   static const HipReductionFunction<T>* bor;
   static const HipReductionFunction<T>* bxor;
+  // float16, bfloat16 and the two float8 types only (refused likewise for the
+  // rest): SUM carried in f32 and rounded once per k-source pass; call(), a
+  // two-operand pass, is SUM
+  static const HipReductionFunction<T>* sum_wide;
 
   explicit HipReductionFunction(ReductionType t) : type_(t) {}
   ReductionType type() const { return type_; }
@@ -116,6 +122,8 @@ template <typename T>
 const HipReductionFunction<T>* HipReductionFunction<T>::bor = new HipReductionFunction<T>(BOR);
 template <typename T>
 const HipReductionFunction<T>* HipReductionFunction<T>::bxor = new HipReductionFunction<T>(BXOR);
+template <typename T>
+const HipReductionFunction<T>* HipReductionFunction<T>::sum_wide = new HipReductionFunction<T>(SUM_WIDE);
 
 // gloo::Algorithm (gloo/algorithm.h:20-38).
 class Algorithm {

@@ -225,10 +225,12 @@ int launchStampInit(uint64_t* stamps, int k, hipStream_t stream);
 // Registered custom reductions (gloo_hip_register_op): op codes
 // GLOO_HIP_CUSTOM + i.  customOp fills fn/user and returns true for a
 // registered code.  isBuiltinOp: the kernels implement `op` on `dtype` (the
-// arithmetic ops on every dtype, the bitwise ops on the integer dtypes).
+// arithmetic ops on every dtype, the bitwise ops on the integer dtypes, the
+// wide sum on f16 / bf16 / f8e4m3 / f8e5m2).
 // checkBitwiseDtype: GLOO_HIP_EINVAL_OP, with a message naming both, for a
-// bitwise op on a floating dtype; GLOO_HIP_OK for every other pair, valid or
-// not (the caller's own op and dtype checks follow).  No GPU call in either.
+// bitwise op on a floating dtype and for GLOO_HIP_SUM_WIDE on a dtype that is
+// none of its four; GLOO_HIP_OK for every other pair, valid or not (the
+// caller's own op and dtype checks follow).  No GPU call in either.
 bool isBuiltinOp(int op, int dtype);
 int checkBitwiseDtype(int op, int dtype);
 bool customOp(int op, gloo_hip_custom_fn* fn, void** user);

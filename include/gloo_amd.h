@@ -61,7 +61,7 @@ extern "C" {
  * collective entry points (gloo_hip_algorithm_create*, gloo_hip_allreduce,
  * gloo_hip_reduce_to_root) before any exchange with a peer, so every rank
  * fails locally.  They take every kernel path the arithmetic ops take.
- * Codes 8..999 are invalid. */
+ * Codes 8..999 are invalid, except GLOO_HIP_SUM_WIDE (257, below). */
 typedef enum {
   GLOO_HIP_SUM = 1,
   GLOO_HIP_PRODUCT = 2,
@@ -71,6 +71,47 @@ typedef enum {
   GLOO_HIP_BOR = 6,
   GLOO_HIP_BXOR = 7,
 } gloo_hip_op_t;
+
+/* Wide sum: the modifier bit GLOO_HIP_WIDE, accepted with SUM only (257, below
+ * the custom range), for F16, BF16, F8E4M3 and F8E5M2 only.  SUM
+ * carried in f32 and rounded to the format once per pass instead of once per
+ * two-operand step (what a GPU allreduce of gradients in a narrow type is
+ * expected to do).  It extends the reference's enum, as the bitwise ops do.
+ *   A pass is one kernel pass over k sources: a plan's FOLD with its
+ *   FOLD_SRCs or a LOCAL_REDUCE; here gloo_hip_reduce_multi or
+ *   gloo_hip_fold_kernel.
+ *   k >= 3: a = f32(s_0); a = a + f32(s_j), j = 1 .. k - 1, each one IEEE
+ *     binary32 add (no contraction, denormals kept), the sources in list
+ *     order; the stored element is narrow(a), the dtype's narrowing applied
+ *     exactly once: round to nearest even; a bf16 NaN is 0x7FC0; FP8 keeps the
+ *     overflow rule and the NaN byte 0x7F above; an f16 NaN is the canonical
+ *     0x7E00 (the F16C operand-payload rule belongs to a two-operand op).
+ *   The fold mode is no association for this op: modes 0 and 1 give the same
+ *     bits (f32 addition commutes) and mode 2 (tree) is evaluated as the same
+ *     left fold, for any k.
+ *   k <= 2, and every two-operand entry point (gloo_hip_reduce,
+ *     gloo_hip_reduce3, gloo_hip_fused_step, gloo_hip_reduce_staged, a plan's
+ *     REDUCE steps) IS SUM, bit for bit.
+ *   More than GLOO_HIP_MAX_SRCS sources are chained folds; every link is a
+ *     pass, so one rounding per link.
+ *   Any other dtype: GLOO_HIP_EINVAL_OP, the message naming the op and the
+ *     dtype, before n or a pointer is looked at and before any exchange, as
+ *     for the bitwise ops.  GLOO_HIP_WIDE with any op but SUM is an unknown op.
+ *     gloo_hip_interp_kernel refuses the op (its folds round per step).
+ *   In a collective the result is a function of the plan alone: every FOLD or
+ *     LOCAL_REDUCE step is one wide pass and every REDUCE is SUM, whatever the
+ *     launch mode, the signalling and profiling.  On the default mesh plans
+ *     (ring-chunked, halving-doubling, reduce-scatter, the new-style RING and
+ *     reduce; one pointer per rank, 2 <= P <= 8) every element is folded once,
+ *     at its owner, so it is rounded exactly once.  The reference routes
+ *     (P > 8, GLOO_AMD_MESH=0), multi-level mesh forms and multi-pointer local
+ *     folds round once per pass.
+ *   e4m3: every input is a multiple of 2^-9 of magnitude <= 448, so every f32
+ *     partial sum of up to 8 inputs is a multiple of 2^-9 below 2^24 * 2^-9,
+ *     i.e. exact: a single pass stores the correctly rounded true sum, in any
+ *     source order. */
+#define GLOO_HIP_WIDE 0x100
+#define GLOO_HIP_SUM_WIDE (GLOO_HIP_SUM | GLOO_HIP_WIDE)
 
 typedef enum {
   GLOO_HIP_I8 = 0,
@@ -111,7 +152,7 @@ typedef enum {
  *   Multi-source folds round to the format after every op (left to right, or
  *     as a tree where the schedule folds as one), so a k-source fold is
  *     byte-identical to k - 1 two-operand calls and every schedule agrees
- *     with its mesh form.
+ *     with its mesh form.  (GLOO_HIP_SUM_WIDE rounds once per pass instead.)
  *   BAND / BOR / BXOR are refused (GLOO_HIP_EINVAL_OP) as for the other
  *     floating dtypes; registered custom ops take them like any known dtype. */
 
@@ -233,7 +274,7 @@ int gloo_hip_fold_kernel(int op, int dtype, void* dst, const void* const* srcs, 
 
 /* 1 when the kernels implement `op` on `dtype`: a built-in op on a dtype it
  * is defined for (SUM..MIN on all twelve, BAND / BOR / BXOR on the six integer
- * dtypes) or a registered custom op on a known dtype; 0 otherwise.  Never
+ * dtypes, SUM_WIDE on F16, BF16, F8E4M3 and F8E5M2) or a registered custom op on a known dtype; 0 otherwise.  Never
  * touches the GPU. */
 int gloo_hip_op_supported(int op, int dtype);
 
