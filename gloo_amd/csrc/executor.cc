@@ -755,7 +755,7 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     const char* im = std::getenv("GLOO_AMD_INTERP");
     const char* gm = std::getenv("GLOO_AMD_GRAPH");
     interpMode_ = deviceSignal_ && !(im && std::string(im) == "0") && !(gm && std::string(gm) == "1") &&
-                  interpBytes() > 0 && !custom_ && !wide_;
+                  interpBytes() > 0 && !custom_;
   }
   // The sliced interpreter's slices spin until their peer slices run, so
   // every launch of the ranks on one GPU must be resident at once.  Measured
@@ -834,6 +834,12 @@ PlanExecutor::PlanExecutor(std::shared_ptr<Context> ctx, int algo, int op, int d
     agreed = std::min(agreed, pr.interpSlices);
   }
   slices_ = agreed > 1 ? agreed : 1;
+  // The wide sum runs on the sliced interpreter only: between rank processes
+  // on one MI355X its one-launch form measured slower than the eager plan it
+  // would replace (P = 4, 64 KiB per rank: 35 us against 25 us), the sliced
+  // form faster (1 MiB: 40 us against 59 us), DESIGN.md §2 "Wide sum".  Every
+  // rank decides alike: the op is part of the call and slices_ is agreed.
+  if (wide_ && slices_ == 1) interpMode_ = false;
   assignSeqs();
   if (deviceSignal_) configureDeviceLaunches();
   } catch (const std::exception& e) {

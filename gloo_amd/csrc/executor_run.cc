@@ -613,8 +613,9 @@ void PlanExecutor::buildInterp() {
     if (bytes > limit) return fail();
     // LOCAL_REDUCE(R), WAIT_RECV, REDUCE(R <- inbox): the wait, then ONE left
     // fold of the pointers and the inbox region, the reference's
-    // ((p0 op p1) ... op p(k-1)) op inbox.  (Sliced: only when R is one piece.)
-    if (fuseLocal && s.kind == GLOO_HIP_STEP_LOCAL_REDUCE && foldsWithReceive(steps, i, ptrs_.size()) &&
+    // ((p0 op p1) ... op p(k-1)) op inbox.  (Sliced: only when R is one piece.
+    // Not the wide sum, as in enqueue(): the plan's REDUCE rounds first.)
+    if (fuseLocal && !wide_ && s.kind == GLOO_HIP_STEP_LOCAL_REDUCE && foldsWithReceive(steps, i, ptrs_.size()) &&
         pieces(s).size() == 1) {
       const Step& rd = steps[i + 2];
       withSeq(push(kInterpWait), i + 1, waitFlag(steps[i + 1].peer, steps[i + 1].slot));

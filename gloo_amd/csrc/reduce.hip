@@ -1158,10 +1158,82 @@ __device__ __forceinline__ void interp_fold(const InterpStep& st, uint64_t lo, u
   for (uint64_t k = t; k < edge; k += kInterpBlock) one(k < head ? k : tail0 + (k - head));
 }
 
+// The wide sum's fold step (GLOO_HIP_SUM_WIDE, "Wide sum" above): interp_fold's
+// split and pass, with the sum carried in f32.  A pass still costs one memory
+// latency: every packet of every source (nsrc x kU, at most 32 packets = 128
+// VGPRs) is requested before the first is used; the packets are then widened
+// and added source by source, in list order, onto kU x kV f32 accumulators per
+// lane (wide_add_packet), narrowed once (wide_narrow_packet) and stored.  The
+// fold mode names no association here (the modes are one left fold), and a
+// lane has loaded every source packet of a pass before it stores that pass, so
+// dst may be any of the sources.  A step of one or two sources IS SUM: it
+// takes interp_fold's two-operand path, chosen per step because a plan mixes
+// its 2-source REDUCEs with k-source FOLDs.
+template <class Tr>
+__device__ __forceinline__ void interp_fold_wide(const InterpStep& st, uint64_t lo, uint64_t hi) {
+  using S = typename Tr::Storage;
+  constexpr int kV = 16 / sizeof(S);
+  constexpr int kU = sizeof(S) == 1 ? 1 : kInterpFoldUnroll;  // as interp_fold: the pass sizes are the same
+  const int ns = st.nsrc;
+  if (ns <= 2) {
+    interp_fold<Tr, GLOO_HIP_SUM>(st, lo, hi);
+    return;
+  }
+  const uint64_t n = hi - lo;
+  const uint64_t t = threadIdx.x;
+  const char* src[GLOO_HIP_MAX_SRCS];
+  char* dstp = st.dst + lo * sizeof(S);
+#pragma unroll
+  for (int j = 0; j < GLOO_HIP_MAX_SRCS; j++) src[j] = j < ns ? st.src[j] + lo * sizeof(S) : nullptr;
+  uint64_t head = ((16 - ((uintptr_t)dstp & 15)) & 15) / sizeof(S);
+  if (head > n) head = n;
+  const uint64_t nv = (n - head) / kV;
+  const uint64_t body = nv * 16;
+  char* dbody = dstp + head * sizeof(S);
+  constexpr uint64_t kPass = (uint64_t)kInterpBlock * kU * 16;
+  const uint32_t lane_off = (uint32_t)t * 16u;
+  for (uint64_t b = 0; b < body; b += kPass) {
+    const uint32_t bytes = (uint32_t)(body - b < kPass ? body - b : kPass);
+    u32x4 v[GLOO_HIP_MAX_SRCS][kU];
+#pragma unroll
+    for (int j = 0; j < GLOO_HIP_MAX_SRCS; j++)
+      if (j < ns) {
+        const Src sj = src_of(src[j] + head * sizeof(S));
+        const auto rj = make_rsrc(sj.base + b, bytes + sj.mis);
+#pragma unroll
+        for (int u = 0; u < kU; u++) v[j][u] = bload<0>(rj, lane_off + u * kInterpBlock * 16, sj.mis);
+      }
+    float a[kU][kV];
+#pragma unroll
+    for (int u = 0; u < kU; u++) wide_add_packet<Tr, true>(v[0][u], a[u]);
+#pragma unroll
+    for (int j = 1; j < GLOO_HIP_MAX_SRCS; j++)
+      if (j < ns) {
+#pragma unroll
+        for (int u = 0; u < kU; u++) wide_add_packet<Tr, false>(v[j][u], a[u]);
+      }
+    const auto rd = make_rsrc(dbody + b, bytes);
+#pragma unroll
+    for (int u = 0; u < kU; u++) bstore<0>(rd, lane_off + u * kInterpBlock * 16, wide_narrow_packet<Tr>(a[u]));
+  }
+  // the head and the ragged tail: wide_elem's fold over the step's pointers
+  const uint64_t tail0 = head + nv * kV, edge = head + (n - tail0);
+  for (uint64_t k = t; k < edge; k += kInterpBlock) {
+    const uint64_t i = k < head ? k : tail0 + (k - head);
+    float e = Tr::widen(reinterpret_cast<const S*>(src[0])[i]);
+#pragma unroll
+    for (int j = 1; j < GLOO_HIP_MAX_SRCS; j++)
+      if (j < ns) e = e + Tr::widen(reinterpret_cast<const S*>(src[j])[i]);
+    reinterpret_cast<S*>(dstp)[i] = wide_narrow<Tr>(e);
+  }
+}
+
+// The step loop of both interpreter kernels; OP == GLOO_HIP_SUM_WIDE takes the
+// wide fold step, everything else is the same code.
 template <class Tr, int OP>
-__global__ __launch_bounds__(kInterpBlock) void plan_interp_kernel(const InterpStep* steps, int nsteps, uint64_t run,
-                                                                   uint64_t timeoutTicks, uint32_t* err,
-                                                                   uint64_t* done, unsigned* doneTicket) {
+__device__ __forceinline__ void plan_interp_body(const InterpStep* steps, int nsteps, uint64_t run,
+                                                 uint64_t timeoutTicks, uint32_t* err, uint64_t* done,
+                                                 unsigned* doneTicket) {
   using S = typename Tr::Storage;
   constexpr uint64_t kV = 16 / sizeof(S);
   __shared__ int ok;
@@ -1209,7 +1281,8 @@ __global__ __launch_bounds__(kInterpBlock) void plan_interp_kernel(const InterpS
       interp_copy(st.dst + lo * sizeof(S), st.src[0] + lo * sizeof(S), (hi - lo) * sizeof(S), st.nxdst, st.xdst,
                   lo * sizeof(S));
     } else if (kind == kInterpFold) {
-      interp_fold<Tr, OP>(st, lo, hi);
+      if constexpr (OP == GLOO_HIP_SUM_WIDE) interp_fold_wide<Tr>(st, lo, hi);
+      else interp_fold<Tr, OP>(st, lo, hi);
     }
     // the next step neither reads nor writes what this one touches: keep
     // this step's memory operations in flight, publish its flag with the batch's
@@ -1246,9 +1319,29 @@ __global__ __launch_bounds__(kInterpBlock) void plan_interp_kernel(const InterpS
   }
 }
 
+template <class Tr, int OP>
+__global__ __launch_bounds__(kInterpBlock) void plan_interp_kernel(const InterpStep* steps, int nsteps, uint64_t run,
+                                                                   uint64_t timeoutTicks, uint32_t* err,
+                                                                   uint64_t* done, unsigned* doneTicket) {
+  plan_interp_body<Tr, OP>(steps, nsteps, run, timeoutTicks, err, done, doneTicket);
+}
+// the same list with the wide sum's fold step (F16, BF16, F8E4M3, F8E5M2 only)
+template <class Tr>
+__global__ __launch_bounds__(kInterpBlock) GLOO_WIDE_KERNEL void plan_interp_wide_kernel(
+    const InterpStep* steps, int nsteps, uint64_t run, uint64_t timeoutTicks, uint32_t* err, uint64_t* done,
+    unsigned* doneTicket) {
+  plan_interp_body<Tr, GLOO_HIP_SUM_WIDE>(steps, nsteps, run, timeoutTicks, err, done, doneTicket);
+}
+
 template <class Tr>
 int launch_interp(int op, const InterpStep* steps, int nsteps, uint64_t run, uint64_t tt, uint32_t* err,
                   int G, hipStream_t s, uint64_t* done, unsigned* dt) {
+  if constexpr (kHasWide<Tr>) {
+    if (op == GLOO_HIP_SUM_WIDE) {
+      plan_interp_wide_kernel<Tr><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt);
+      return GLOO_HIP_OK;
+    }
+  }
   switch (op) {
     case GLOO_HIP_SUM: plan_interp_kernel<Tr, GLOO_HIP_SUM><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt); break;
     case GLOO_HIP_PRODUCT: plan_interp_kernel<Tr, GLOO_HIP_PRODUCT><<<G, kInterpBlock, 0, s>>>(steps, nsteps, run, tt, err, done, dt); break;
@@ -2201,7 +2294,7 @@ int launchPlanInterp(int op, int dtype, const InterpStep* steps, int nsteps, uin
     default: return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   }
   if (rc != GLOO_HIP_OK) return set_error(rc, "interpreter: bad op");
-  return check_launch("plan_interp_kernel");
+  return check_launch(op == GLOO_HIP_SUM_WIDE ? "plan_interp_wide_kernel" : "plan_interp_kernel");
 }
 
 }  // namespace gloo_amd
@@ -2352,8 +2445,6 @@ int gloo_hip_interp_kernel(int op, int dtype, const gloo_hip_interp_step_t* step
   if (es == 0) return set_error(GLOO_HIP_EINVAL_DTYPE, "unknown dtype");
   if (const int rc = checkBitwiseDtype(op, dtype)) return rc;
   if (!isBuiltinOp(op, dtype)) return set_error(GLOO_HIP_EINVAL_OP, "the interpreter takes a built-in op");
-  if (op == GLOO_HIP_SUM_WIDE)  // its folds round per two-operand step; the executor keeps the op off it too
-    return set_error(GLOO_HIP_EINVAL_OP, "the interpreter does not run sum_wide (a plan with it is replayed or enqueued)");
   std::vector<InterpStep> v((size_t)nsteps);
   for (int i = 0; i < nsteps; i++) {
     const gloo_hip_interp_step_t& s = steps[i];
@@ -2364,7 +2455,7 @@ int gloo_hip_interp_kernel(int op, int dtype, const gloo_hip_interp_step_t* step
     if (s.mode < 0 || s.mode > 2) return bad(GLOO_HIP_EINVAL_ARG, i, "unknown fold mode " + std::to_string(s.mode));
     if (fold && (s.nsrc < 1 || s.nsrc > GLOO_HIP_MAX_SRCS))
       return bad(GLOO_HIP_EINVAL_ARG, i, "source count " + std::to_string(s.nsrc) + " outside [1, 8]");
-    if (fold && s.mode == 2 && (s.nsrc & (s.nsrc - 1)))
+    if (fold && s.mode == 2 && (s.nsrc & (s.nsrc - 1)) && op != GLOO_HIP_SUM_WIDE)  // (no association for the wide sum)
       return bad(GLOO_HIP_EINVAL_ARG, i, "tree fold needs a power-of-two count, not " + std::to_string(s.nsrc));
     if (s.defer != 0 && s.defer != 1) return bad(GLOO_HIP_EINVAL_ARG, i, "defer bit " + std::to_string(s.defer));
     if (s.defer && i == nsteps - 1) return bad(GLOO_HIP_EINVAL_ARG, i, "defer bit on the last step");

@@ -191,8 +191,10 @@ class PlanExecutor {
   bool custom_ = false;  // op_ is a registered custom reduction (gloo_hip_register_op)
   // op_ is GLOO_HIP_SUM_WIDE: every FOLD / LOCAL_REDUCE is one wide pass and
   // every REDUCE is SUM, so nothing may merge or split the plan's arithmetic
-  // passes: no interpreter (its folds round per step) and no local fold +
-  // receive-reduce pass; the bits are then the plan's in every launch mode
+  // passes: no local fold + receive-reduce pass, and the interpreter folds a
+  // step of k >= 3 sources as one wide pass (plan_interp_wide_kernel); the
+  // bits are then the plan's in every launch mode.  (Only the sliced
+  // interpreter runs the op: the one-launch form measured slower, executor.cc.)
   bool wide_ = false;
   int planAlgo_;  // the plan executed (RING_CHUNKED may run as RING_CHUNKED_MESH)
   size_t es_;

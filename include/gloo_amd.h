@@ -97,7 +97,8 @@ typedef enum {
  *   Any other dtype: GLOO_HIP_EINVAL_OP, the message naming the op and the
  *     dtype, before n or a pointer is looked at and before any exchange, as
  *     for the bitwise ops.  GLOO_HIP_WIDE with any op but SUM is an unknown op.
- *     gloo_hip_interp_kernel refuses the op (its folds round per step).
+ *     By gloo_hip_interp_kernel the op is accepted: a fold step of k >= 3
+ *     sources is one wide pass (plan_interp_wide_kernel), k <= 2 IS SUM.
  *   In a collective the result is a function of the plan alone: every FOLD or
  *     LOCAL_REDUCE step is one wide pass and every REDUCE is SUM, whatever the
  *     launch mode, the signalling and profiling.  On the default mesh plans
@@ -680,7 +681,8 @@ typedef struct {
  * ends its workgroup: no later step, no later flag, no done.  done /
  * done_ticket (both or neither; the ticket a zeroed device word): the
  * workgroup finishing last stores `run` to *done and leaves the ticket at 0.
- * Built-in ops only.  Every argument and every step is checked before any
+ * Built-in ops only; GLOO_HIP_SUM_WIDE is accepted for its four dtypes (a fold
+ * step is then a wide pass, and its mode 2 takes any nsrc).  Every argument and every step is checked before any
  * GPU call (the last-error text names the step and the value): kind, mode,
  * nsrc, the defer bit (0 / 1, never on the last step, never between a wait
  * and a step that is none), a flag on send / signal / wait, and with n > 0
