@@ -51,6 +51,18 @@ class DType(enum.IntEnum):
     F8E5M2 = 11  # OCP e5m2 (torch.float8_e5m2)
 
 
+class MXFormat(enum.IntEnum):
+    """gloo_hip_mx_format_t: the OCP Microscaling formats of reduce_mx (include/gloo_amd.h
+    "MX block-scaled sum"): blocks of 32 elements, one E8M0 scale byte each."""
+    MXFP8_E4M3 = 0  # e4m3fn elements, 32 bytes per block
+    MXFP8_E5M2 = 1  # e5m2 elements, 32 bytes per block
+    MXFP4_E2M1 = 2  # e2m1 elements, two per byte (torch.float4_e2m1fn_x2), 16 bytes per block
+
+
+MX_FORMAT_NAMES = {"mxfp8_e4m3": MXFormat.MXFP8_E4M3, "mxfp8_e5m2": MXFormat.MXFP8_E5M2,
+                   "mxfp4_e2m1": MXFormat.MXFP4_E2M1}
+MX_BLOCK_BYTES = {MXFormat.MXFP8_E4M3: 32, MXFormat.MXFP8_E5M2: 32, MXFormat.MXFP4_E2M1: 16}
+
 DTYPE_NAMES = {"i8": DType.I8, "u8": DType.U8, "i32": DType.I32, "u32": DType.U32,
                "i64": DType.I64, "u64": DType.U64, "f16": DType.F16, "bf16": DType.BF16,
                "f32": DType.F32, "f64": DType.F64, "f8e4m3": DType.F8E4M3, "f8e5m2": DType.F8E5M2}
@@ -65,7 +77,8 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_set_variant", "gloo_hip_plan", "gloo_hip_reduce_staged", "gloo_hip_register_op",
             "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
             "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel",
-            "gloo_hip_interp_kernel", "gloo_hip_fused_step")
+            "gloo_hip_interp_kernel", "gloo_hip_fused_step", "gloo_hip_reduce_mx", "gloo_hip_mx_supported",
+            "gloo_hip_mx_tile_blocks")
 MAX_SRCS, MAX_XDSTS = 8, 8  # include/gloo_amd.h GLOO_HIP_MAX_SRCS, GLOO_HIP_MAX_XDSTS
 
 
@@ -122,10 +135,16 @@ def _load():
                                          ctypes.c_int, u64, vp, vp, vp, vp]
     L.gloo_hip_fused_step.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, sz, vp, u64, u64, u64, vp, vp, u64, u64, vp,
                                       vp]
+    L.gloo_hip_reduce_mx.argtypes = [ctypes.c_int, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int, sz, vp]
+    L.gloo_hip_mx_supported.argtypes = [ctypes.c_int]
+    L.gloo_hip_mx_tile_blocks.argtypes = [ctypes.c_int]
+    L.gloo_hip_mx_tile_blocks.restype = sz
     return L
 
 
 lib = _load()
+# blocks per workgroup tile of reduce_mx's kernel, per format (the lengths around which its last tile is cut)
+MX_TILE_BLOCKS = {f: lib.gloo_hip_mx_tile_blocks(int(f)) for f in MXFormat}
 
 
 def _check(rc):
@@ -174,6 +193,28 @@ def reduce_multi_ptr(op, dtype, dst, srcs, n, stream=0):
     arr = (ctypes.c_void_p * len(srcs))(*srcs)
     _check(lib.gloo_hip_reduce_multi(_as_op(op), _as_dtype(dtype), dst, arr, len(srcs), n,
                                      stream or None))
+
+
+def _as_mx(fmt):
+    return int(MX_FORMAT_NAMES[fmt]) if isinstance(fmt, str) else int(fmt)
+
+
+def mx_supported(fmt):
+    """gloo_hip_mx_supported: is `fmt` one of the MX formats of reduce_mx?  Never touches the GPU."""
+    return bool(lib.gloo_hip_mx_supported(_as_mx(fmt)))
+
+
+def reduce_mx_ptr(fmt, dst_elems, dst_scales, src_elems, src_scales, nblocks, stream=0):
+    """gloo_hip_reduce_mx on device pointers: dst = the block-scaled sum of the
+    k sources (k pointers in src_elems, k in src_scales), nblocks blocks of 32
+    elements, one pass, asynchronous on `stream`.  dst may be source 0."""
+    k = len(src_elems)
+    if len(src_scales) != k:
+        raise ValueError("one scale array per element array")
+    vp = ctypes.c_void_p
+    _check(lib.gloo_hip_reduce_mx(_as_mx(fmt), dst_elems or None, dst_scales or None,
+                                  (vp * k)(*[p or None for p in src_elems]), (vp * k)(*[p or None for p in src_scales]),
+                                  k, nblocks, stream or None))
 
 
 def reduce_staged(op, dtype, host_dst, host_src, n, dev_dst, dev_src, piece_elems=0, stream=0):
@@ -334,6 +375,32 @@ def reduce3(op, c, a, b, stream=None):
     reduce3_ptr(op, _torch_dtype_code(c), c.data_ptr(), a.data_ptr(), b.data_ptr(), c.numel(),
                 _stream_handle(c, stream))
     return c
+
+
+def _mx_pair(fmt, pair):
+    """(elems, scales) as byte views, checked against each other: -> (elems, scales, nblocks)."""
+    import torch
+    elems, scales = (t if t.dtype == torch.uint8 else t.view(torch.uint8) for t in pair)
+    if not (elems.is_cuda and scales.is_cuda and elems.is_contiguous() and scales.is_contiguous()):
+        raise ValueError("MX elements and scales must be contiguous device tensors")
+    if elems.numel() != scales.numel() * MX_BLOCK_BYTES[MXFormat(_as_mx(fmt))]:
+        raise ValueError(f"{elems.numel()} element bytes do not go with {scales.numel()} scale bytes")
+    return elems, scales, scales.numel()
+
+
+def reduce_mx(fmt, dst, srcs, stream=None):
+    """dst = the MX block-scaled sum of srcs (include/gloo_amd.h "MX block-scaled
+    sum"), one pass.  dst and every source are (elems, scales) pairs of
+    contiguous device tensors: uint8, or the matching float8 / float4 dtype
+    for the elements and float8_e8m0fnu for the scales, taken as bytes.  dst
+    may be srcs[0]."""
+    de, ds, nblocks = _mx_pair(fmt, dst)
+    pairs = [_mx_pair(fmt, s) for s in srcs]
+    if any(n != nblocks for _, _, n in pairs):
+        raise ValueError("dst and every source must hold the same number of blocks")
+    reduce_mx_ptr(fmt, de.data_ptr(), ds.data_ptr(), [e.data_ptr() for e, _, _ in pairs],
+                  [s.data_ptr() for _, s, _ in pairs], nblocks, _stream_handle(de, stream))
+    return dst
 
 
 class ReductionFunction:
@@ -785,6 +852,28 @@ def allgather(ctx, output, elements, dtype, input=None, counts=None, tag=0, stre
     o.tag = tag
     o.stream = stream or None
     _check(lib.gloo_hip_allgather(ctx._h, ctypes.byref(o)))
+
+
+def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0):
+    """MX block-scaled allreduce, the one-shot form, for 2 <= P <= 8 ranks:
+    every rank's (elems, scales) becomes the MX sum of all ranks' buffers.
+    Plain composition: two allgathers (U8) into the caller's scratch
+    (gathered_elems / gathered_scales: P times the bytes of elems / scales),
+    then ONE reduce_mx over the P gathered sources in rank order, so every
+    rank folds the same bytes in the same order and stores identical bytes.
+    Each rank moves P blocks per block of its own.  Tensors as in reduce_mx;
+    `stream` is a stream handle as in allgather (0: the default stream)."""
+    P = ctx.size
+    if not 2 <= P <= MAX_SRCS:
+        raise ValueError(f"allreduce_mx takes 2..{MAX_SRCS} ranks, not {P}")
+    e, s, nblocks = _mx_pair(fmt, (elems, scales))
+    ge, gs, gblocks = _mx_pair(fmt, (gathered_elems, gathered_scales))
+    if gblocks != P * nblocks:
+        raise ValueError(f"the gathered scratch holds {gblocks} blocks, not {P} x {nblocks}")
+    allgather(ctx, ge.data_ptr(), e.numel(), "u8", input=e.data_ptr(), tag=tag, stream=stream)
+    allgather(ctx, gs.data_ptr(), s.numel(), "u8", input=s.data_ptr(), tag=tag, stream=stream)
+    reduce_mx_ptr(fmt, e.data_ptr(), s.data_ptr(), [ge.data_ptr() + r * e.numel() for r in range(P)],
+                  [gs.data_ptr() + r * s.numel() for r in range(P)], nblocks, stream)
 
 
 # ---- new-style function API: gloo::gather(opts) / gloo::gatherv(opts) / gloo::scatter(opts) --

@@ -38,14 +38,13 @@
 #include <type_traits>
 #include <vector>
 
+#include "buffer_rsrc.h"
 #include "gloo_amd.h"
 #include "gloo_amd/errors.h"
 #include "gloo_amd/signal.h"
 
 namespace gloo_amd {
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------
 // Element traits.  S = storage type.  Integers compute in the unsigned type of
@@ -390,15 +389,6 @@ __device__ __forceinline__ u32x4 apply_packet<TrF8E5M2, GLOO_HIP_PRODUCT>(u32x4 
   return f8_pk_packet<TrF8E5M2, GLOO_HIP_PRODUCT>(a, b);
 }
 
-// Buffer resources.  Each workgroup builds descriptors whose base is its own
-// tile (wave-uniform, SGPRs) and whose range is the bytes left in the body, so
-// 32-bit lane offsets suffice for any chunk size and the hardware range check
-// drops the out-of-range packets of a ragged last tile (loads return 0, stores
-// are discarded) without per-lane branches.
-constexpr int kRsrcFlags = 0x00020000;  // gfx950 raw-buffer word 3
-constexpr int kAuxNT = 2;               // cache policy `nt`: streamed once
-constexpr int kAuxWT = 1 | 2 | 16;      // `sc0 nt sc1`: streamed once, written through (not held in L2)
-
 // Completion protocol of the kernels that signal a peer after writing into
 // its inbox (copy_signal_kernel, fold_send_kernel, the interpreter): the
 // signalled bytes are stored write-through (sc0 nt sc1) and every wave waits
@@ -410,13 +400,6 @@ constexpr int kAuxWT = 1 | 2 | 16;      // `sc0 nt sc1`: streamed once, written 
 // in every workgroup: 4x slower at 16 MiB; that protocol and its
 // switch are gone.)
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, kRsrcFlags);
-}
-template <int AUX>
-__device__ __forceinline__ u32x4 bload(__amdgpu_buffer_rsrc_t r, uint32_t off, uint32_t soff = 0) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, AUX);
-}
 
 // A source operand of the vector body: its first body byte sits `mis` bytes
 // past a 16-B boundary (0 when it is congruent with the destination).  The
@@ -431,10 +414,6 @@ struct Src {
 __device__ __forceinline__ Src src_of(const void* body) {
   const uintptr_t p = reinterpret_cast<uintptr_t>(body);
   return Src{reinterpret_cast<const char*>(p & ~uintptr_t(15)), (uint32_t)(p & 15)};
-}
-template <int AUX>
-__device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, uint32_t off, u32x4 v, uint32_t soff = 0) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, soff, AUX);
 }
 
 // Element-wise head / tail: elements [0, head) and [tail0, n) of the chunk,
@@ -735,12 +714,6 @@ __device__ __forceinline__ void fold_tile(const SrcList& srcs, int k, size_t hea
 // v_cvt_pk_f32_fp8 / _bf8 (two elements each), shift / mask of the dword for
 // bf16, the two halves of the dword for f16.
 // ---------------------------------------------------------------------------
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GLOO_WIDE_KERNEL __attribute__((target("no-packed-fp32-ops")))
-#else
-#define GLOO_WIDE_KERNEL
-#endif
-
 template <class Tr>
 constexpr bool kHasWide = std::is_same<Tr, TrF16>::value || std::is_same<Tr, TrBF16>::value ||
                           std::is_same<Tr, TrF8E4M3>::value || std::is_same<Tr, TrF8E5M2>::value;

@@ -125,6 +125,27 @@ const HipReductionFunction<T>* HipReductionFunction<T>::bxor = new HipReductionF
 template <typename T>
 const HipReductionFunction<T>* HipReductionFunction<T>::sum_wide = new HipReductionFunction<T>(SUM_WIDE);
 
+// MX block-scaled sum (include/gloo_amd.h "MX block-scaled sum"): one buffer
+// is its element array and its E8M0 scale array, one byte per 32 elements.
+struct MxBuffer {
+  void* elems;
+  uint8_t* scales;
+};
+// dst = the requantised f32 sum of srcs (1..GLOO_HIP_MAX_SRCS of them), nblocks
+// blocks each, one pass enqueued on `stream`; dst may be srcs[0].
+inline void reduceMx(gloo_hip_mx_format_t fmt, const MxBuffer& dst, const std::vector<MxBuffer>& srcs, size_t nblocks,
+                     hipStream_t stream) {
+  std::vector<const void*> elems;
+  std::vector<const uint8_t*> scales;
+  for (const MxBuffer& s : srcs) {
+    elems.push_back(s.elems);
+    scales.push_back(s.scales);
+  }
+  const int rc = gloo_hip_reduce_mx(fmt, dst.elems, dst.scales, elems.data(), scales.data(), (int)srcs.size(), nblocks,
+                                    stream);
+  if (rc != GLOO_HIP_OK) throw EnforceNotMet(gloo_hip_last_error());
+}
+
 // gloo::Algorithm (gloo/algorithm.h:20-38).
 class Algorithm {
  public:

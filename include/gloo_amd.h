@@ -114,6 +114,59 @@ typedef enum {
 #define GLOO_HIP_WIDE 0x100
 #define GLOO_HIP_SUM_WIDE (GLOO_HIP_SUM | GLOO_HIP_WIDE)
 
+/* MX block-scaled sum (gloo_hip_reduce_mx, below): SUM over buffers kept in an
+ * OCP Microscaling format.  A buffer is TWO arrays: the elements, and one
+ * E8M0 scale byte X per block of 32 consecutive elements, worth 2^(X - 127);
+ * X = 255 is NaN.  It extends the reference's type list, as FP8 does; the
+ * wide sum's convention (accumulate in f32, narrow once per pass) carries
+ * over, with a dequantise in front and a per-block requantise behind.
+ *
+ *   format                code  elements  emax  max normal  bytes per block
+ *   GLOO_HIP_MXFP8_E4M3   0     e4m3fn    8     448         32
+ *   GLOO_HIP_MXFP8_E5M2   1     e5m2      15    57344       32
+ *   GLOO_HIP_MXFP4_E2M1   2     e2m1      2     6           16
+ *
+ *   Element values are the OCP tables; e4m3fn and e5m2 widen as F8E4M3 and
+ *   F8E5M2 do.  MXFP4 packs two elements per byte, element 2i in the LOW
+ *   nibble of byte i (the layout of torch.float4_e2m1fn_x2).
+ *
+ * The model, for one block and k sources in list order, 1 <= k <=
+ * GLOO_HIP_MAX_SRCS:
+ *   dequantise   v_j[i] = f32(elem_j[i]) * f32(2^(X_j - 127)): one IEEE
+ *                binary32 multiply, denormals kept (2^-127 is the f32
+ *                denormal 0x00400000).
+ *   accumulate   a[i] = v_0[i]; a[i] = a[i] + v_j[i], j = 1 .. k - 1: each one
+ *                binary32 add, no contraction, exactly as in SUM_WIDE.
+ *   NaN block    any X_j == 255, or any a[i] a NaN or +-inf.  Its stored scale
+ *                is 255 and every stored element the format's canonical NaN,
+ *                byte 0x7F for both FP8 element types.  e2m1 has no NaN: every
+ *                stored nibble is 0 (byte 0x00) and the scale alone carries it.
+ *   scale        of a finite block: amax = max_i |a[i]|, F = the binary32
+ *                exponent field of amax (0 for zero and for denormals), X_out
+ *                = max(F - emax, 0): the OCP specification's floor rule; an
+ *                all-zero block stores scale 0.
+ *   elements     of a finite block: q[i] = a[i] * 2^(127 - X_out) (exact, or
+ *                rounding towards zero far below the element's resolution),
+ *                clamped to +-max normal, rounded to nearest even into the
+ *                element type.  The stored sign is a[i]'s, also where the
+ *                magnitude rounds to zero (all three element types have -0).
+ *   MX elements SATURATE, as in the OCP specification and torchao: amax's
+ *   mantissa can put q up to just below 2^(emax + 1), above max normal.  The
+ *   plain FP8 dtypes of this library (F8E4M3, F8E5M2 above) do NOT saturate.
+ *
+ * The only op is SUM.  One pass is one requantisation; k = 1 requantises the
+ * source to its canonical scale.  The destination arrays may BE source 0's (in
+ * place: the same addresses); any other byte shared between a destination
+ * array and another array of the call is refused.  Element arrays are 16-byte
+ * aligned, scale arrays start at any byte.  The length is in blocks: there is
+ * no ragged head or tail. */
+typedef enum {
+  GLOO_HIP_MXFP8_E4M3 = 0,
+  GLOO_HIP_MXFP8_E5M2 = 1,
+  GLOO_HIP_MXFP4_E2M1 = 2,
+  GLOO_HIP_NUM_MX_FORMATS = 3,
+} gloo_hip_mx_format_t;
+
 typedef enum {
   GLOO_HIP_I8 = 0,
   GLOO_HIP_U8 = 1,
@@ -190,6 +243,25 @@ int gloo_hip_reduce3(int op, int dtype, void* c, const void* a, const void* b,
 int gloo_hip_reduce_multi(int op, int dtype, void* dst,
                           const void* const* srcs, int k, size_t n,
                           gloo_hip_stream_t stream);
+
+/* MX block-scaled sum ("MX block-scaled sum" above): dst = the requantised f32
+ * sum of k sources, nblocks blocks of 32 elements each, in ONE pass and one
+ * launch, asynchronous on `stream`; it never allocates.  src_elems and
+ * src_scales are HOST arrays of k device pointers.  Every argument is checked
+ * before any GPU call, and the last-error text names the value: an unknown
+ * format is GLOO_HIP_EINVAL_DTYPE; k outside 1..GLOO_HIP_MAX_SRCS
+ * GLOO_HIP_EINVAL_ARG; with nblocks > 0, a null pointer or an element pointer
+ * that is not 16-byte aligned GLOO_HIP_EINVAL_PTR and a forbidden overlap
+ * GLOO_HIP_EINVAL_ARG.  nblocks == 0 launches nothing. */
+int gloo_hip_reduce_mx(int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
+                       const uint8_t* const* src_scales, int k, size_t nblocks, gloo_hip_stream_t stream);
+
+/* 1 when fmt is one of the three MX formats, 0 otherwise.  Never touches the GPU. */
+int gloo_hip_mx_supported(int fmt);
+
+/* (new, tests) Blocks per workgroup tile of gloo_hip_reduce_mx's kernel for
+ * `fmt` (0: unknown format): the lengths around which its last tile is cut. */
+size_t gloo_hip_mx_tile_blocks(int fmt);
 
 /* Host-staged chunk reduction: host_dst[i] = host_dst[i] (op) host_src[i]
  * for a chunk that starts and ends in (pinned) host memory — a transport's
