@@ -78,7 +78,8 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_copy_kernel", "gloo_hip_copy_kernel_multi", "gloo_hip_op_supported",
             "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel",
             "gloo_hip_interp_kernel", "gloo_hip_fused_step", "gloo_hip_reduce_mx", "gloo_hip_mx_supported",
-            "gloo_hip_mx_tile_blocks")
+            "gloo_hip_mx_tile_blocks", "gloo_hip_quantise_mx", "gloo_hip_reduce_mx_wide",
+            "gloo_hip_mx_quantise_tile_blocks", "gloo_hip_mx_wide_tile_blocks")
 MAX_SRCS, MAX_XDSTS = 8, 8  # include/gloo_amd.h GLOO_HIP_MAX_SRCS, GLOO_HIP_MAX_XDSTS
 
 
@@ -139,6 +140,11 @@ def _load():
     L.gloo_hip_mx_supported.argtypes = [ctypes.c_int]
     L.gloo_hip_mx_tile_blocks.argtypes = [ctypes.c_int]
     L.gloo_hip_mx_tile_blocks.restype = sz
+    L.gloo_hip_quantise_mx.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, sz, vp]
+    L.gloo_hip_reduce_mx_wide.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int,
+                                          sz, vp]
+    for f in (L.gloo_hip_mx_quantise_tile_blocks, L.gloo_hip_mx_wide_tile_blocks):
+        f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int], sz
     return L
 
 
@@ -215,6 +221,34 @@ def reduce_mx_ptr(fmt, dst_elems, dst_scales, src_elems, src_scales, nblocks, st
     _check(lib.gloo_hip_reduce_mx(_as_mx(fmt), dst_elems or None, dst_scales or None,
                                   (vp * k)(*[p or None for p in src_elems]), (vp * k)(*[p or None for p in src_scales]),
                                   k, nblocks, stream or None))
+
+
+def mx_quantise_tile_blocks(fmt, dtype):
+    """Blocks per workgroup tile of quantise_mx's kernel (0: unknown format or not a wide dtype)."""
+    return lib.gloo_hip_mx_quantise_tile_blocks(_as_mx(fmt), _as_dtype(dtype))
+
+
+def mx_wide_tile_blocks(fmt, dtype):
+    """Blocks per workgroup tile of reduce_mx_wide's kernel (0: unknown format or not a wide dtype)."""
+    return lib.gloo_hip_mx_wide_tile_blocks(_as_mx(fmt), _as_dtype(dtype))
+
+
+def quantise_mx_ptr(fmt, dtype, dst_elems, dst_scales, src, nblocks, stream=0):
+    """gloo_hip_quantise_mx on device pointers: (dst_elems, dst_scales) = the MX
+    form of nblocks blocks of 32 elements of `dtype` (f32, f16 or bf16) at src."""
+    _check(lib.gloo_hip_quantise_mx(_as_mx(fmt), _as_dtype(dtype), dst_elems or None, dst_scales or None, src or None,
+                                    nblocks, stream or None))
+
+
+def reduce_mx_wide_ptr(fmt, dtype, dst, src_elems, src_scales, nblocks, stream=0):
+    """gloo_hip_reduce_mx_wide on device pointers: dst = the f32 sum of the k MX
+    sources narrowed once to `dtype` (f32, f16 or bf16), nblocks * 32 elements."""
+    k = len(src_elems)
+    if len(src_scales) != k:
+        raise ValueError("one scale array per element array")
+    vp = ctypes.c_void_p
+    _check(lib.gloo_hip_reduce_mx_wide(_as_mx(fmt), _as_dtype(dtype), dst or None, (vp * k)(*[p or None for p in src_elems]),
+                                       (vp * k)(*[p or None for p in src_scales]), k, nblocks, stream or None))
 
 
 def reduce_staged(op, dtype, host_dst, host_src, n, dev_dst, dev_src, piece_elems=0, stream=0):
@@ -401,6 +435,46 @@ def reduce_mx(fmt, dst, srcs, stream=None):
     reduce_mx_ptr(fmt, de.data_ptr(), ds.data_ptr(), [e.data_ptr() for e, _, _ in pairs],
                   [s.data_ptr() for _, s, _ in pairs], nblocks, _stream_handle(de, stream))
     return dst
+
+
+def _mx_wide(t, nblocks):
+    """A wide tensor of the quantise / the wide fold: -> its dtype code."""
+    import torch
+    codes = {torch.float32: DType.F32, torch.float16: DType.F16, torch.bfloat16: DType.BF16}
+    if t.dtype not in codes:
+        raise TypeError(f"MX quantise and wide fold take float32, float16 or bfloat16, not {t.dtype}")
+    if not (t.is_cuda and t.is_contiguous()):
+        raise ValueError("the wide tensor must be a contiguous device tensor")
+    if t.numel() % 32 or t.numel() // 32 != nblocks:
+        raise ValueError(f"{t.numel()} elements are not {nblocks} blocks of 32")
+    return codes[t.dtype]
+
+
+def quantise_mx(fmt, dst, src, stream=None):
+    """dst = the MX form of src (include/gloo_amd.h "MX quantise and wide-output
+    fold"): dst an (elems, scales) pair as in reduce_mx, src a contiguous device
+    tensor of float32, float16 or bfloat16 whose numel is a multiple of 32."""
+    de, ds, nblocks = _mx_pair(fmt, dst)
+    quantise_mx_ptr(fmt, _mx_wide(src, nblocks), de.data_ptr(), ds.data_ptr(), src.data_ptr(), nblocks,
+                    _stream_handle(src, stream))
+    return dst
+
+
+def reduce_mx_wide(fmt, dst, srcs, stream=None):
+    """dst = the f32 sum of the MX pairs in srcs narrowed once to dst's dtype
+    (float32, float16 or bfloat16), one pass."""
+    pairs = [_mx_pair(fmt, s) for s in srcs]
+    nblocks = pairs[0][2] if pairs else 0
+    if any(n != nblocks for _, _, n in pairs):
+        raise ValueError("every source must hold the same number of blocks")
+    reduce_mx_wide_ptr(fmt, _mx_wide(dst, nblocks), dst.data_ptr(), [e.data_ptr() for e, _, _ in pairs],
+                       [s.data_ptr() for _, s, _ in pairs], nblocks, _stream_handle(dst, stream))
+    return dst
+
+
+def dequantise_mx(fmt, dst, pair, stream=None):
+    """dst = the wide form of one MX pair: the wide fold with k = 1."""
+    return reduce_mx_wide(fmt, dst, [pair], stream)
 
 
 class ReductionFunction:
@@ -874,6 +948,28 @@ def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0
     allgather(ctx, gs.data_ptr(), s.numel(), "u8", input=s.data_ptr(), tag=tag, stream=stream)
     reduce_mx_ptr(fmt, e.data_ptr(), s.data_ptr(), [ge.data_ptr() + r * e.numel() for r in range(P)],
                   [gs.data_ptr() + r * s.numel() for r in range(P)], nblocks, stream)
+
+
+def allreduce_via_mx(ctx, fmt, tensor, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0):
+    """Allreduce (SUM) of a float32 / float16 / bfloat16 tensor through an MX
+    wire format, for 2 <= P <= 8 ranks: quantise `tensor` into the caller's
+    (elems, scales), the two U8 allgathers of allreduce_mx, then ONE
+    reduce_mx_wide over the P gathered sources in rank order into `tensor`.
+    Each element is quantised once, at its sender, and rounded once, at the
+    end; every rank stores identical bytes.  Scratch as in allreduce_mx."""
+    P = ctx.size
+    if not 2 <= P <= MAX_SRCS:
+        raise ValueError(f"allreduce_via_mx takes 2..{MAX_SRCS} ranks, not {P}")
+    e, s, nblocks = _mx_pair(fmt, (elems, scales))
+    ge, gs, gblocks = _mx_pair(fmt, (gathered_elems, gathered_scales))
+    if gblocks != P * nblocks:
+        raise ValueError(f"the gathered scratch holds {gblocks} blocks, not {P} x {nblocks}")
+    dtype = _mx_wide(tensor, nblocks)
+    quantise_mx_ptr(fmt, dtype, e.data_ptr(), s.data_ptr(), tensor.data_ptr(), nblocks, stream)
+    allgather(ctx, ge.data_ptr(), e.numel(), "u8", input=e.data_ptr(), tag=tag, stream=stream)
+    allgather(ctx, gs.data_ptr(), s.numel(), "u8", input=s.data_ptr(), tag=tag, stream=stream)
+    reduce_mx_wide_ptr(fmt, dtype, tensor.data_ptr(), [ge.data_ptr() + r * e.numel() for r in range(P)],
+                       [gs.data_ptr() + r * s.numel() for r in range(P)], nblocks, stream)
 
 
 # ---- new-style function API: gloo::gather(opts) / gloo::gatherv(opts) / gloo::scatter(opts) --

@@ -1,5 +1,5 @@
 // buffer_rsrc.h — raw buffer loads / stores of 16-byte packets, shared by the
-// kernel translation units (reduce.hip, mx.hip).  Internal: device code only.
+// kernel translation units (reduce.hip, mx.hip, mx_quant.hip). Internal: device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

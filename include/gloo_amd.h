@@ -159,7 +159,28 @@ typedef enum {
  * place: the same addresses); any other byte shared between a destination
  * array and another array of the call is refused.  Element arrays are 16-byte
  * aligned, scale arrays start at any byte.  The length is in blocks: there is
- * no ragged head or tail. */
+ * no ragged head or tail.
+ *
+ * MX quantise and wide-output fold (gloo_hip_quantise_mx and
+ * gloo_hip_reduce_mx_wide, below): the two ends of that path for tensors held
+ * in a wide dtype, GLOO_HIP_F32, GLOO_HIP_F16 or GLOO_HIP_BF16.  Formats,
+ * blocks, scale bytes and the e2m1 nibble order are the ones above.
+ *   quantise     a[i] = f32(src[i]) (exact, f16 denormals included), then the
+ *                NaN block, scale and elements steps above applied to a: it is
+ *                the MX sum with k = 1 whose dequantised source is the wide
+ *                block itself.  A block with any NaN or +-inf input stores
+ *                scale 255 and the format's NaN fill, an all-zero block scale 0.
+ *   wide fold    dequantise and accumulate exactly as above, then dst[i] =
+ *                narrow_dtype(a[i]), applied once: f32 is stored as is; bf16
+ *                and f16 round to nearest even as in SUM_WIDE (an f16 overflow
+ *                becomes inf); +-inf stays.  Every NaN is stored as the dtype's
+ *                canonical quiet NaN (0x7FC00000, 0x7FC0, 0x7E00), and where
+ *                any source's scale byte for a block is 255 all 32 outputs of
+ *                the block are that NaN.  k = 1 is the dequantise.
+ * Neither has an in-place form (the sizes differ): any byte shared between a
+ * destination array and a source array, or between the two destination arrays
+ * of the quantise, is refused.  Element arrays and wide arrays are 16-byte
+ * aligned, scale arrays start at any byte, lengths are in blocks. */
 typedef enum {
   GLOO_HIP_MXFP8_E4M3 = 0,
   GLOO_HIP_MXFP8_E5M2 = 1,
@@ -262,6 +283,29 @@ int gloo_hip_mx_supported(int fmt);
 /* (new, tests) Blocks per workgroup tile of gloo_hip_reduce_mx's kernel for
  * `fmt` (0: unknown format): the lengths around which its last tile is cut. */
 size_t gloo_hip_mx_tile_blocks(int fmt);
+
+/* MX quantise ("MX quantise and wide-output fold" above): (dst_elems,
+ * dst_scales) = the MX form of nblocks blocks of 32 elements of `dtype` at
+ * src, one launch, asynchronous on `stream`; it never allocates.  Arguments
+ * are checked as gloo_hip_reduce_mx checks its own, before any GPU call, the
+ * last-error text naming the value: an unknown format, or a dtype other than
+ * F32 / F16 / BF16, is GLOO_HIP_EINVAL_DTYPE; with nblocks > 0, a null pointer
+ * or a dst_elems / src that is not 16-byte aligned GLOO_HIP_EINVAL_PTR and a
+ * shared byte GLOO_HIP_EINVAL_ARG.  nblocks == 0 launches nothing. */
+int gloo_hip_quantise_mx(int fmt, int dtype, void* dst_elems, uint8_t* dst_scales, const void* src, size_t nblocks,
+                         gloo_hip_stream_t stream);
+
+/* Wide-output MX fold (same paragraph): dst = the f32 sum of k MX sources
+ * narrowed once to `dtype`, nblocks * 32 elements, one pass and one launch.
+ * src_elems and src_scales are HOST arrays of k device pointers.  Checked as
+ * above; k outside 1..GLOO_HIP_MAX_SRCS is GLOO_HIP_EINVAL_ARG. */
+int gloo_hip_reduce_mx_wide(int fmt, int dtype, void* dst, const void* const* src_elems, const uint8_t* const* src_scales,
+                            int k, size_t nblocks, gloo_hip_stream_t stream);
+
+/* (new, tests) Blocks per workgroup tile of the two kernels above (0: unknown
+ * format or a dtype that is not wide). */
+size_t gloo_hip_mx_quantise_tile_blocks(int fmt, int dtype);
+size_t gloo_hip_mx_wide_tile_blocks(int fmt, int dtype);
 
 /* Host-staged chunk reduction: host_dst[i] = host_dst[i] (op) host_src[i]
  * for a chunk that starts and ends in (pinned) host memory — a transport's
