@@ -79,7 +79,8 @@ EXPORTED = ("gloo_hip_reduce", "gloo_hip_reduce3", "gloo_hip_reduce_multi",
             "gloo_hip_fanout_kernel", "gloo_hip_gather_fanout_kernel", "gloo_hip_fold_kernel",
             "gloo_hip_interp_kernel", "gloo_hip_fused_step", "gloo_hip_reduce_mx", "gloo_hip_mx_supported",
             "gloo_hip_mx_tile_blocks", "gloo_hip_quantise_mx", "gloo_hip_reduce_mx_wide",
-            "gloo_hip_mx_quantise_tile_blocks", "gloo_hip_mx_wide_tile_blocks")
+            "gloo_hip_mx_quantise_tile_blocks", "gloo_hip_mx_wide_tile_blocks", "gloo_hip_quantise_mx_sr",
+            "gloo_hip_reduce_mx_sr")
 MAX_SRCS, MAX_XDSTS = 8, 8  # include/gloo_amd.h GLOO_HIP_MAX_SRCS, GLOO_HIP_MAX_XDSTS
 
 
@@ -145,6 +146,8 @@ def _load():
                                           sz, vp]
     for f in (L.gloo_hip_mx_quantise_tile_blocks, L.gloo_hip_mx_wide_tile_blocks):
         f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int], sz
+    L.gloo_hip_quantise_mx_sr.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, sz, u64, vp]
+    L.gloo_hip_reduce_mx_sr.argtypes = [ctypes.c_int, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int, sz, u64, vp]
     return L
 
 
@@ -210,17 +213,24 @@ def mx_supported(fmt):
     return bool(lib.gloo_hip_mx_supported(_as_mx(fmt)))
 
 
-def reduce_mx_ptr(fmt, dst_elems, dst_scales, src_elems, src_scales, nblocks, stream=0):
+def _seeded(seed):
+    """The arguments a stochastic-rounding entry point takes in front of its stream: none, or the seed mod 2^64."""
+    return () if seed is None else (int(seed) % 2 ** 64,)
+
+
+def reduce_mx_ptr(fmt, dst_elems, dst_scales, src_elems, src_scales, nblocks, stream=0, seed=None):
     """gloo_hip_reduce_mx on device pointers: dst = the block-scaled sum of the
     k sources (k pointers in src_elems, k in src_scales), nblocks blocks of 32
-    elements, one pass, asynchronous on `stream`.  dst may be source 0."""
+    elements, one pass, asynchronous on `stream`.  dst may be source 0.  An int
+    `seed` is gloo_hip_reduce_mx_sr: the requantise rounds stochastically
+    (include/gloo_amd.h "MX stochastic rounding")."""
     k = len(src_elems)
     if len(src_scales) != k:
         raise ValueError("one scale array per element array")
     vp = ctypes.c_void_p
-    _check(lib.gloo_hip_reduce_mx(_as_mx(fmt), dst_elems or None, dst_scales or None,
-                                  (vp * k)(*[p or None for p in src_elems]), (vp * k)(*[p or None for p in src_scales]),
-                                  k, nblocks, stream or None))
+    fn = lib.gloo_hip_reduce_mx if seed is None else lib.gloo_hip_reduce_mx_sr
+    _check(fn(_as_mx(fmt), dst_elems or None, dst_scales or None, (vp * k)(*[p or None for p in src_elems]),
+              (vp * k)(*[p or None for p in src_scales]), k, nblocks, *_seeded(seed), stream or None))
 
 
 def mx_quantise_tile_blocks(fmt, dtype):
@@ -233,11 +243,13 @@ def mx_wide_tile_blocks(fmt, dtype):
     return lib.gloo_hip_mx_wide_tile_blocks(_as_mx(fmt), _as_dtype(dtype))
 
 
-def quantise_mx_ptr(fmt, dtype, dst_elems, dst_scales, src, nblocks, stream=0):
+def quantise_mx_ptr(fmt, dtype, dst_elems, dst_scales, src, nblocks, stream=0, seed=None):
     """gloo_hip_quantise_mx on device pointers: (dst_elems, dst_scales) = the MX
-    form of nblocks blocks of 32 elements of `dtype` (f32, f16 or bf16) at src."""
-    _check(lib.gloo_hip_quantise_mx(_as_mx(fmt), _as_dtype(dtype), dst_elems or None, dst_scales or None, src or None,
-                                    nblocks, stream or None))
+    form of nblocks blocks of 32 elements of `dtype` (f32, f16 or bf16) at src.
+    An int `seed` is gloo_hip_quantise_mx_sr: stochastic rounding."""
+    fn = lib.gloo_hip_quantise_mx if seed is None else lib.gloo_hip_quantise_mx_sr
+    _check(fn(_as_mx(fmt), _as_dtype(dtype), dst_elems or None, dst_scales or None, src or None, nblocks, *_seeded(seed),
+              stream or None))
 
 
 def reduce_mx_wide_ptr(fmt, dtype, dst, src_elems, src_scales, nblocks, stream=0):
@@ -422,18 +434,18 @@ def _mx_pair(fmt, pair):
     return elems, scales, scales.numel()
 
 
-def reduce_mx(fmt, dst, srcs, stream=None):
+def reduce_mx(fmt, dst, srcs, stream=None, seed=None):
     """dst = the MX block-scaled sum of srcs (include/gloo_amd.h "MX block-scaled
     sum"), one pass.  dst and every source are (elems, scales) pairs of
     contiguous device tensors: uint8, or the matching float8 / float4 dtype
     for the elements and float8_e8m0fnu for the scales, taken as bytes.  dst
-    may be srcs[0]."""
+    may be srcs[0].  seed: None rounds to nearest even, an int stochastically."""
     de, ds, nblocks = _mx_pair(fmt, dst)
     pairs = [_mx_pair(fmt, s) for s in srcs]
     if any(n != nblocks for _, _, n in pairs):
         raise ValueError("dst and every source must hold the same number of blocks")
     reduce_mx_ptr(fmt, de.data_ptr(), ds.data_ptr(), [e.data_ptr() for e, _, _ in pairs],
-                  [s.data_ptr() for _, s, _ in pairs], nblocks, _stream_handle(de, stream))
+                  [s.data_ptr() for _, s, _ in pairs], nblocks, _stream_handle(de, stream), seed)
     return dst
 
 
@@ -450,13 +462,15 @@ def _mx_wide(t, nblocks):
     return codes[t.dtype]
 
 
-def quantise_mx(fmt, dst, src, stream=None):
+def quantise_mx(fmt, dst, src, stream=None, seed=None):
     """dst = the MX form of src (include/gloo_amd.h "MX quantise and wide-output
     fold"): dst an (elems, scales) pair as in reduce_mx, src a contiguous device
-    tensor of float32, float16 or bfloat16 whose numel is a multiple of 32."""
+    tensor of float32, float16 or bfloat16 whose numel is a multiple of 32.
+    seed: None rounds to nearest even, an int stochastically ("MX stochastic
+    rounding"), reproducibly for that seed."""
     de, ds, nblocks = _mx_pair(fmt, dst)
     quantise_mx_ptr(fmt, _mx_wide(src, nblocks), de.data_ptr(), ds.data_ptr(), src.data_ptr(), nblocks,
-                    _stream_handle(src, stream))
+                    _stream_handle(src, stream), seed)
     return dst
 
 
@@ -928,7 +942,7 @@ def allgather(ctx, output, elements, dtype, input=None, counts=None, tag=0, stre
     _check(lib.gloo_hip_allgather(ctx._h, ctypes.byref(o)))
 
 
-def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0):
+def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0, seed=None):
     """MX block-scaled allreduce, the one-shot form, for 2 <= P <= 8 ranks:
     every rank's (elems, scales) becomes the MX sum of all ranks' buffers.
     Plain composition: two allgathers (U8) into the caller's scratch
@@ -936,7 +950,9 @@ def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0
     then ONE reduce_mx over the P gathered sources in rank order, so every
     rank folds the same bytes in the same order and stores identical bytes.
     Each rank moves P blocks per block of its own.  Tensors as in reduce_mx;
-    `stream` is a stream handle as in allgather (0: the default stream)."""
+    `stream` is a stream handle as in allgather (0: the default stream).  An
+    int `seed` folds with stochastic rounding; every rank passes the same seed,
+    so the identical bytes stay identical."""
     P = ctx.size
     if not 2 <= P <= MAX_SRCS:
         raise ValueError(f"allreduce_mx takes 2..{MAX_SRCS} ranks, not {P}")
@@ -947,16 +963,18 @@ def allreduce_mx(ctx, fmt, elems, scales, gathered_elems, gathered_scales, tag=0
     allgather(ctx, ge.data_ptr(), e.numel(), "u8", input=e.data_ptr(), tag=tag, stream=stream)
     allgather(ctx, gs.data_ptr(), s.numel(), "u8", input=s.data_ptr(), tag=tag, stream=stream)
     reduce_mx_ptr(fmt, e.data_ptr(), s.data_ptr(), [ge.data_ptr() + r * e.numel() for r in range(P)],
-                  [gs.data_ptr() + r * s.numel() for r in range(P)], nblocks, stream)
+                  [gs.data_ptr() + r * s.numel() for r in range(P)], nblocks, stream, seed)
 
 
-def allreduce_via_mx(ctx, fmt, tensor, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0):
+def allreduce_via_mx(ctx, fmt, tensor, elems, scales, gathered_elems, gathered_scales, tag=0, stream=0, seed=None):
     """Allreduce (SUM) of a float32 / float16 / bfloat16 tensor through an MX
     wire format, for 2 <= P <= 8 ranks: quantise `tensor` into the caller's
     (elems, scales), the two U8 allgathers of allreduce_mx, then ONE
     reduce_mx_wide over the P gathered sources in rank order into `tensor`.
     Each element is quantised once, at its sender, and rounded once, at the
-    end; every rank stores identical bytes.  Scratch as in allreduce_mx."""
+    end; every rank stores identical bytes.  Scratch as in allreduce_mx.  An
+    int `seed` quantises with stochastic rounding, rank r from seed + r (mod
+    2^64), so that ranks do not share their rounding decisions."""
     P = ctx.size
     if not 2 <= P <= MAX_SRCS:
         raise ValueError(f"allreduce_via_mx takes 2..{MAX_SRCS} ranks, not {P}")
@@ -965,7 +983,8 @@ def allreduce_via_mx(ctx, fmt, tensor, elems, scales, gathered_elems, gathered_s
     if gblocks != P * nblocks:
         raise ValueError(f"the gathered scratch holds {gblocks} blocks, not {P} x {nblocks}")
     dtype = _mx_wide(tensor, nblocks)
-    quantise_mx_ptr(fmt, dtype, e.data_ptr(), s.data_ptr(), tensor.data_ptr(), nblocks, stream)
+    quantise_mx_ptr(fmt, dtype, e.data_ptr(), s.data_ptr(), tensor.data_ptr(), nblocks, stream,
+                    None if seed is None else seed + ctx.rank)
     allgather(ctx, ge.data_ptr(), e.numel(), "u8", input=e.data_ptr(), tag=tag, stream=stream)
     allgather(ctx, gs.data_ptr(), s.numel(), "u8", input=s.data_ptr(), tag=tag, stream=stream)
     reduce_mx_wide_ptr(fmt, dtype, tensor.data_ptr(), [ge.data_ptr() + r * e.numel() for r in range(P)],

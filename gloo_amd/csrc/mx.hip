@@ -38,6 +38,12 @@
 // overflow included: the same bytes.  amax is the unsigned
 // maximum of the accumulators' magnitude bits, so one compare against
 // 0x7F800000 finds any inf or NaN of the block.
+//
+// Rounding mode.  mx_fold_kernel<FMT, SR>: SR = false is the above; SR = true
+// (gloo_hip_reduce_mx_sr, "MX stochastic rounding") narrows with
+// mx_narrow_packet_sr of mx_common.h from the packet's first element index and
+// the seed's key, the one argument only that instantiation reads.  Everything
+// in front of the narrowing is shared.
 
 #include <hip/hip_runtime.h>
 
@@ -56,9 +62,9 @@
 namespace gloo_amd {
 namespace {
 
-template <int FMT>
+template <int FMT, bool SR>
 __global__ __launch_bounds__(kMxBlock) GLOO_WIDE_KERNEL void mx_fold_kernel(void* dstE, uint8_t* dstS, MxSrcList srcs,
-                                                                             int k, size_t nblocks) {
+                                                                             int k, size_t nblocks, uint32_t key) {
   using F = MxFmt<FMT>;
   constexpr int U = F::kUnroll;
   const size_t block0 = (size_t)blockIdx.x * F::kTileBlocks;
@@ -105,7 +111,13 @@ __global__ __launch_bounds__(kMxBlock) GLOO_WIDE_KERNEL void mx_fold_kernel(void
     const bool finite = m < 0x7F800000u;
     const uint32_t f = m >> 23;  // 0 for zero and denormals
     const uint32_t Xfin = f > (uint32_t)F::kEmax ? f - (uint32_t)F::kEmax : 0u;
-    u32x4 out = mx_narrow_packet<FMT>(a[u], finite ? Xfin : 0u);
+    u32x4 out;
+    if constexpr (SR) {  // key is read here only; the packet's first element of the whole tensor
+      const size_t pkt = (size_t)blockIdx.x * (kMxBlock * U) + threadIdx.x + u * kMxBlock;
+      out = mx_narrow_packet_sr<FMT>(a[u], finite ? Xfin : 0u, pkt * F::kAcc, key);
+    } else {
+      out = mx_narrow_packet<FMT>(a[u], finite ? Xfin : 0u);
+    }
     if (!finite) out = u32x4{F::kNanFill, F::kNanFill, F::kNanFill, F::kNanFill};
     bstore<kAuxNT>(rd, lane_off + u * kMxBlock * 16, out);
     if (F::kLanesPerBlock == 1 || (threadIdx.x & 1) == 0)
@@ -113,7 +125,6 @@ __global__ __launch_bounds__(kMxBlock) GLOO_WIDE_KERNEL void mx_fold_kernel(void
   }
 }
 
-int mxError(int code, const std::string& msg) { return setError(code, "reduce_mx: " + msg); }
 
 std::string hex(const void* p) {
   char buf[32];
@@ -128,34 +139,23 @@ struct Range {
 bool overlap(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
 
 template <int FMT>
-int launchMx(void* dstE, uint8_t* dstS, const MxSrcList& list, int k, size_t nblocks, hipStream_t s) {
+int launchMx(const std::string& fn, void* dstE, uint8_t* dstS, const MxSrcList& list, int k, size_t nblocks, const uint64_t* seed,
+             hipStream_t s) {
   const size_t grid = (nblocks + MxFmt<FMT>::kTileBlocks - 1) / MxFmt<FMT>::kTileBlocks;
-  if (grid > 0x7FFFFFFFu) return mxError(GLOO_HIP_EINVAL_ARG, "nblocks " + std::to_string(nblocks) + " is too large for one launch");
-  mx_fold_kernel<FMT><<<dim3((unsigned)grid), dim3(kMxBlock), 0, s>>>(dstE, dstS, list, k, nblocks);
+  if (grid > 0x7FFFFFFFu)
+    return setError(GLOO_HIP_EINVAL_ARG, fn + ": nblocks " + std::to_string(nblocks) + " is too large for one launch");
+  const dim3 g((unsigned)grid), b(kMxBlock);
+  if (seed) mx_fold_kernel<FMT, true><<<g, b, 0, s>>>(dstE, dstS, list, k, nblocks, mxSeedKey(*seed));
+  else mx_fold_kernel<FMT, false><<<g, b, 0, s>>>(dstE, dstS, list, k, nblocks, 0u);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return setError((int)e, std::string("mx_fold_kernel: ") + hipGetErrorString(e));
   return GLOO_HIP_OK;
 }
 
-}  // namespace
-}  // namespace gloo_amd
-
-extern "C" {
-
-int gloo_hip_mx_supported(int fmt) { return fmt >= GLOO_HIP_MXFP8_E4M3 && fmt <= GLOO_HIP_MXFP4_E2M1 ? 1 : 0; }
-
-size_t gloo_hip_mx_tile_blocks(int fmt) {
-  switch (fmt) {
-    case GLOO_HIP_MXFP8_E4M3: return gloo_amd::MxFmt<GLOO_HIP_MXFP8_E4M3>::kTileBlocks;
-    case GLOO_HIP_MXFP8_E5M2: return gloo_amd::MxFmt<GLOO_HIP_MXFP8_E5M2>::kTileBlocks;
-    case GLOO_HIP_MXFP4_E2M1: return gloo_amd::MxFmt<GLOO_HIP_MXFP4_E2M1>::kTileBlocks;
-    default: return 0;
-  }
-}
-
-int gloo_hip_reduce_mx(int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
-                       const uint8_t* const* src_scales, int k, size_t nblocks, gloo_hip_stream_t stream) {
-  using namespace gloo_amd;
+// both rounding modes of the sum: `seed` is null for round to nearest even
+int reduceMx(const std::string& fn, int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
+             const uint8_t* const* src_scales, int k, size_t nblocks, const uint64_t* seed, gloo_hip_stream_t stream) {
+  auto mxError = [&](int code, const std::string& msg) { return setError(code, fn + ": " + msg); };
   if (!gloo_hip_mx_supported(fmt)) return mxError(GLOO_HIP_EINVAL_DTYPE, "unknown MX format " + std::to_string(fmt));
   if (k < 1 || k > GLOO_HIP_MAX_SRCS)
     return mxError(GLOO_HIP_EINVAL_ARG, "source count " + std::to_string(k) + " is outside 1.." + std::to_string(GLOO_HIP_MAX_SRCS));
@@ -191,10 +191,36 @@ int gloo_hip_reduce_mx(int fmt, void* dst_elems, uint8_t* dst_scales, const void
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (fmt) {
-    case GLOO_HIP_MXFP8_E4M3: return launchMx<GLOO_HIP_MXFP8_E4M3>(dst_elems, dst_scales, list, k, nblocks, s);
-    case GLOO_HIP_MXFP8_E5M2: return launchMx<GLOO_HIP_MXFP8_E5M2>(dst_elems, dst_scales, list, k, nblocks, s);
-    default: return launchMx<GLOO_HIP_MXFP4_E2M1>(dst_elems, dst_scales, list, k, nblocks, s);
+    case GLOO_HIP_MXFP8_E4M3: return launchMx<GLOO_HIP_MXFP8_E4M3>(fn, dst_elems, dst_scales, list, k, nblocks, seed, s);
+    case GLOO_HIP_MXFP8_E5M2: return launchMx<GLOO_HIP_MXFP8_E5M2>(fn, dst_elems, dst_scales, list, k, nblocks, seed, s);
+    default: return launchMx<GLOO_HIP_MXFP4_E2M1>(fn, dst_elems, dst_scales, list, k, nblocks, seed, s);
   }
+}
+
+}  // namespace
+}  // namespace gloo_amd
+
+extern "C" {
+
+int gloo_hip_mx_supported(int fmt) { return fmt >= GLOO_HIP_MXFP8_E4M3 && fmt <= GLOO_HIP_MXFP4_E2M1 ? 1 : 0; }
+
+size_t gloo_hip_mx_tile_blocks(int fmt) {
+  switch (fmt) {
+    case GLOO_HIP_MXFP8_E4M3: return gloo_amd::MxFmt<GLOO_HIP_MXFP8_E4M3>::kTileBlocks;
+    case GLOO_HIP_MXFP8_E5M2: return gloo_amd::MxFmt<GLOO_HIP_MXFP8_E5M2>::kTileBlocks;
+    case GLOO_HIP_MXFP4_E2M1: return gloo_amd::MxFmt<GLOO_HIP_MXFP4_E2M1>::kTileBlocks;
+    default: return 0;
+  }
+}
+
+int gloo_hip_reduce_mx(int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
+                       const uint8_t* const* src_scales, int k, size_t nblocks, gloo_hip_stream_t stream) {
+  return gloo_amd::reduceMx("reduce_mx", fmt, dst_elems, dst_scales, src_elems, src_scales, k, nblocks, nullptr, stream);
+}
+
+int gloo_hip_reduce_mx_sr(int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
+                          const uint8_t* const* src_scales, int k, size_t nblocks, uint64_t seed, gloo_hip_stream_t stream) {
+  return gloo_amd::reduceMx("reduce_mx_sr", fmt, dst_elems, dst_scales, src_elems, src_scales, k, nblocks, &seed, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // mx_common.h — the MX (OCP Microscaling) device helpers shared by mx.hip (the
 // block-scaled sum) and mx_quant.hip (quantise, wide-output fold): the format
-// table, the scale, the dequantising add, the requantising narrow and a
-// source's request.  Moved textually out of mx.hip; the arithmetic and the
+// table, the scale, the dequantising add, the requantising narrow in its two
+// rounding modes and a source's request.  Moved textually out of mx.hip; the arithmetic and the
 // GLOO_MX_SCALED_CVT switch are described at the head of that file.
 // Internal: device code only.
 #pragma once
@@ -113,6 +113,42 @@ __device__ __forceinline__ uint32_t fp4_code(float q) {
   return ((uint32_t)__builtin_rintf(t) + off) | ((__builtin_bit_cast(uint32_t, q) >> 28) & 8u);
 }
 
+// One dword of elements from its kPerDword values: divided by sc on the way
+// where the converts are the scaled ones (sc is ignored otherwise).
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_convert_dword(const float (&q)[MxFmt<FMT>::kAcc / 4], float sc) {
+  using F = MxFmt<FMT>;
+  constexpr int kPerDword = F::kAcc / 4;
+  if constexpr (kScaledNarrow) {
+    if constexpr (F::kFp4) {
+      uint32_t r = 0;
+      r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[0], q[1], sc, 0);
+      r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[2], q[3], sc, 1);
+      r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[4], q[5], sc, 2);
+      return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[6], q[7], sc, 3);
+    } else {
+      i16x2 r = {0, 0};
+      if constexpr (F::kE5M2) {
+        r = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(r, q[0], q[1], sc, false);
+        r = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(r, q[2], q[3], sc, true);
+      } else {
+        r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, q[0], q[1], sc, false);
+        r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, q[2], q[3], sc, true);
+      }
+      return __builtin_bit_cast(uint32_t, r);
+    }
+  } else if constexpr (F::kFp4) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int e = 0; e < kPerDword; e++) r |= fp4_code(q[e]) << (4 * e);
+    return r;
+  } else if constexpr (F::kE5M2) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(q[2], q[3], __builtin_amdgcn_cvt_pk_bf8_f32(q[0], q[1], 0, false), true);
+  } else {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false), true);
+  }
+}
+
 // The accumulators of one packet requantised with the block's X_out.
 template <int FMT>
 __device__ __forceinline__ u32x4 mx_narrow_packet(const float (&a)[MxFmt<FMT>::kAcc], uint32_t Xout) {
@@ -129,41 +165,74 @@ __device__ __forceinline__ u32x4 mx_narrow_packet(const float (&a)[MxFmt<FMT>::k
       const float lim = F::kMax * mx_scale(Xout);
 #pragma unroll
       for (int e = 0; e < kPerDword; e++) q[e] = __builtin_amdgcn_fmed3f(a[kPerDword * d + e], -lim, lim);
-      const float sc = mx_scale(Xout);
-      if constexpr (F::kFp4) {
-        uint32_t r = 0;
-        r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[0], q[1], sc, 0);
-        r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[2], q[3], sc, 1);
-        r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[4], q[5], sc, 2);
-        w[d] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, q[6], q[7], sc, 3);
-      } else {
-        i16x2 r = {0, 0};
-        if constexpr (F::kE5M2) {
-          r = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(r, q[0], q[1], sc, false);
-          r = __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(r, q[2], q[3], sc, true);
-        } else {
-          r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, q[0], q[1], sc, false);
-          r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, q[2], q[3], sc, true);
-        }
-        w[d] = __builtin_bit_cast(uint32_t, r);
-      }
     } else {
 #pragma unroll
       for (int e = 0; e < kPerDword; e++)
         q[e] = __builtin_amdgcn_fmed3f(a[kPerDword * d + e] * inv, -F::kMax, F::kMax);
-      if constexpr (F::kFp4) {
-        uint32_t r = 0;
-#pragma unroll
-        for (int e = 0; e < kPerDword; e++) r |= fp4_code(q[e]) << (4 * e);
-        w[d] = r;
-      } else if constexpr (F::kE5M2) {
-        w[d] = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(q[2], q[3], __builtin_amdgcn_cvt_pk_bf8_f32(q[0], q[1], 0, false),
-                                                         true);
-      } else {
-        w[d] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false),
-                                                         true);
-      }
     }
+    w[d] = mx_convert_dword<FMT>(q, mx_scale(Xout));
+  }
+  return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// MurmurHash3's finaliser
+__host__ __device__ __forceinline__ uint32_t mx_fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  return h ^ h >> 16;
+}
+
+// K of a call's seed, computed once on the host
+inline uint32_t mxSeedKey(uint64_t seed) { return mx_fmix32((uint32_t)seed) ^ (uint32_t)(seed >> 32); }
+
+// The stochastic elements step (include/gloo_amd.h "MX stochastic rounding")
+// on the binary32 bits of one clamped q: the on-grid value it stores.  The
+// significand, implicit bit in front, is shifted down until 16 bits stay below
+// the element's grid unit: 7 - M bits from the element's smallest normal
+// binade up, one more per binade below it, and for 24 or more nothing is left
+// (an f32 denormal's false implicit bit included).  What stays is the
+// truncated magnitude t in grid units above frac16, so the 16 random bits
+// added to it carry into t exactly when frac16 + R16 >= 2^16, and t times the
+// unit is exact: t = 2^(M + 1) is the next binade's first value.
+template <int FMT>
+__device__ __forceinline__ float mx_sr_element(float q, uint32_t r16) {
+  using F = MxFmt<FMT>;
+  constexpr uint32_t M = F::kFp4 ? 1 : F::kE5M2 ? 2 : 3;                 // mantissa bits
+  constexpr uint32_t kMinNormal = F::kFp4 ? 127 : F::kE5M2 ? 113 : 121;  // f32 exponent field of the smallest normal
+  const uint32_t bits = __builtin_bit_cast(uint32_t, q), E = (bits >> 23) & 0xFFu;
+  const uint32_t binade = E > kMinNormal ? E : kMinNormal;
+  const uint32_t shift = binade - E + (7 - M);
+  const uint32_t sig = (bits & 0x007FFFFFu) | 0x00800000u;
+  const uint32_t t = ((sig >> (shift < 24 ? shift : 24)) + r16) >> 16;
+  const float mag = (float)t * __builtin_bit_cast(float, (binade - M) << 23);
+  return __builtin_copysignf(mag, q);
+}
+
+// mx_narrow_packet with stochastic rounding: `first` is the global index of
+// a[0], a multiple of the number of accumulators in use (8 or the packet's),
+// so the packet's pairs share the high word of their index; key is the host's
+// K.  One hash serves two neighbouring elements.  The values handed to the
+// converts are on the element grid already: scale 1, and no rounding is left.
+template <int FMT>
+__device__ __forceinline__ u32x4 mx_narrow_packet_sr(const float (&a)[MxFmt<FMT>::kAcc], uint32_t Xout, size_t first,
+                                                     uint32_t key) {
+  using F = MxFmt<FMT>;
+  constexpr int kPerDword = F::kAcc / 4;
+  const float inv = __builtin_bit_cast(float, (254u - Xout) << 23);
+  const uint32_t pair0 = (uint32_t)(first >> 1), high = 0x9E3779B9u * (uint32_t)(first >> 33);
+  uint32_t w[4];
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    float q[kPerDword];
+#pragma unroll
+    for (int e = 0; e < kPerDword; e += 2) {
+      const uint32_t W = mx_fmix32(((pair0 + (uint32_t)(kPerDword * d + e) / 2) ^ key) + high);
+      q[e] = mx_sr_element<FMT>(__builtin_amdgcn_fmed3f(a[kPerDword * d + e] * inv, -F::kMax, F::kMax), W & 0xFFFFu);
+      q[e + 1] = mx_sr_element<FMT>(__builtin_amdgcn_fmed3f(a[kPerDword * d + e + 1] * inv, -F::kMax, F::kMax), W >> 16);
+    }
+    w[d] = mx_convert_dword<FMT>(q, 1.0f);
   }
   return u32x4{w[0], w[1], w[2], w[3]};
 }

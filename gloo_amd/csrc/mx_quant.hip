@@ -4,7 +4,7 @@
 // blocks, scales and nibble order are the MX block-scaled sum's (mx.hip), and
 // so are the device helpers of mx_common.h.
 //
-// mx_quantise_kernel<FMT, DTYPE>: (elements, E8M0 scales) = quantise(wide src).
+// mx_quantise_kernel<FMT, DTYPE, SR>: (elements, E8M0 scales) = quantise(wide src).
 //   Traffic per block: 128 (f32) or 64 bytes read, 32 (FP8) or 16 (FP4) + 1
 //   written.  A lane owns 8 consecutive elements of a row: one b128 load for
 //   f16 / bf16, two adjacent ones for f32.  Four lanes are a block, and blocks
@@ -20,6 +20,9 @@
 //   The widening goes through f32 for every dtype (exact: bits, a shift, or
 //   v_cvt_f32_f16, denormals included); gfx950's direct
 //   v_cvt_scalef32_pk_{fp8,bf8,fp4}_{f16,bf16} converts are not used.
+//   The third template parameter is the rounding mode: SR = true
+//   (gloo_hip_quantise_mx_sr) narrows with mx_narrow_packet_sr from the row's
+//   first element index and the seed's key, which only it reads.
 //
 // mx_fold_wide_kernel<FMT, DTYPE>: dst = narrow_dtype(sum_j dequantise(src_j)).
 //   The source side is mx_fold_kernel's: the same tile, packets, accumulator
@@ -77,9 +80,9 @@ struct MxWide {
   }
 };
 
-template <int FMT, int DTYPE>
+template <int FMT, int DTYPE, bool SR>
 __global__ __launch_bounds__(kMxBlock) GLOO_WIDE_KERNEL void mx_quantise_kernel(void* dstE, uint8_t* dstS, const void* src,
-                                                                                 size_t nblocks) {
+                                                                                 size_t nblocks, uint32_t key) {
   using F = MxFmt<FMT>;
   using W = MxWide<DTYPE>;
   constexpr uint32_t kOut = F::kFp4 ? 4 : 8;      // element bytes a lane stores per row
@@ -126,7 +129,10 @@ __global__ __launch_bounds__(kMxBlock) GLOO_WIDE_KERNEL void mx_quantise_kernel(
     const bool finite = m < 0x7F800000u;
     const uint32_t f = m >> 23;  // 0 for zero and denormals
     const uint32_t Xfin = f > (uint32_t)F::kEmax ? f - (uint32_t)F::kEmax : 0u;
-    u32x4 out = mx_narrow_packet<FMT>(q, finite ? Xfin : 0u);
+    u32x4 out;
+    if constexpr (SR)  // key is read here only; the row's first element of the whole tensor
+      out = mx_narrow_packet_sr<FMT>(q, finite ? Xfin : 0u, (block0 * 4 + threadIdx.x + r * kMxBlock) * 8, key);
+    else out = mx_narrow_packet<FMT>(q, finite ? Xfin : 0u);
     if (!finite) out.x = F::kNanFill, out.y = F::kNanFill;
     const uint32_t row = threadIdx.x + r * kMxBlock;
     if constexpr (F::kFp4) __builtin_amdgcn_raw_buffer_store_b32(out.x, rd, row * kOut, 0, kAuxNT);
@@ -268,6 +274,26 @@ int launchStatus(const char* kernel) {
   return e == hipSuccess ? GLOO_HIP_OK : setError((int)e, std::string(kernel) + ": " + hipGetErrorString(e));
 }
 
+// both rounding modes of the quantise: `seed` is null for round to nearest even
+int quantiseMx(const std::string& fn, int fmt, int dtype, void* dst_elems, uint8_t* dst_scales, const void* src, size_t nblocks,
+               const uint64_t* seed, gloo_hip_stream_t stream) {
+  if (const int rc = checkFormatAndDtype(fn, fmt, dtype)) return rc;
+  if (nblocks == 0) return GLOO_HIP_OK;
+  const size_t ebytes = nblocks * (fmt == GLOO_HIP_MXFP4_E2M1 ? 16 : 32), wbytes = nblocks * 32 * (dtype == GLOO_HIP_F32 ? 4 : 2);
+  const Range dst[2] = {{"dst_elems", "", dst_elems, ebytes, true}, {"dst_scales", "", dst_scales, nblocks, false}};
+  const Range from = {"src", "", src, wbytes, true};
+  if (const int rc = checkRanges(fn, dst, 2, &from, 1)) return rc;
+  const size_t grid = (nblocks + kQTileBlocks - 1) / kQTileBlocks;
+  if (const int rc = checkGrid(fn, grid, nblocks)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return withFormatAndDtype(fmt, dtype, [&](auto F, auto D) {
+    const dim3 g((unsigned)grid), b(kMxBlock);
+    if (seed) mx_quantise_kernel<F(), D(), true><<<g, b, 0, s>>>(dst_elems, dst_scales, src, nblocks, mxSeedKey(*seed));
+    else mx_quantise_kernel<F(), D(), false><<<g, b, 0, s>>>(dst_elems, dst_scales, src, nblocks, 0u);
+    return launchStatus("mx_quantise_kernel");
+  });
+}
+
 }  // namespace
 }  // namespace gloo_amd
 
@@ -281,21 +307,12 @@ size_t gloo_hip_mx_wide_tile_blocks(int fmt, int dtype) { return gloo_amd::wideD
 
 int gloo_hip_quantise_mx(int fmt, int dtype, void* dst_elems, uint8_t* dst_scales, const void* src, size_t nblocks,
                          gloo_hip_stream_t stream) {
-  using namespace gloo_amd;
-  const std::string fn = "quantise_mx";
-  if (const int rc = checkFormatAndDtype(fn, fmt, dtype)) return rc;
-  if (nblocks == 0) return GLOO_HIP_OK;
-  const size_t ebytes = nblocks * (fmt == GLOO_HIP_MXFP4_E2M1 ? 16 : 32), wbytes = nblocks * 32 * (dtype == GLOO_HIP_F32 ? 4 : 2);
-  const Range dst[2] = {{"dst_elems", "", dst_elems, ebytes, true}, {"dst_scales", "", dst_scales, nblocks, false}};
-  const Range from = {"src", "", src, wbytes, true};
-  if (const int rc = checkRanges(fn, dst, 2, &from, 1)) return rc;
-  const size_t grid = (nblocks + kQTileBlocks - 1) / kQTileBlocks;
-  if (const int rc = checkGrid(fn, grid, nblocks)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return withFormatAndDtype(fmt, dtype, [&](auto F, auto D) {
-    mx_quantise_kernel<F(), D()><<<dim3((unsigned)grid), dim3(kMxBlock), 0, s>>>(dst_elems, dst_scales, src, nblocks);
-    return launchStatus("mx_quantise_kernel");
-  });
+  return gloo_amd::quantiseMx("quantise_mx", fmt, dtype, dst_elems, dst_scales, src, nblocks, nullptr, stream);
+}
+
+int gloo_hip_quantise_mx_sr(int fmt, int dtype, void* dst_elems, uint8_t* dst_scales, const void* src, size_t nblocks,
+                            uint64_t seed, gloo_hip_stream_t stream) {
+  return gloo_amd::quantiseMx("quantise_mx_sr", fmt, dtype, dst_elems, dst_scales, src, nblocks, &seed, stream);
 }
 
 int gloo_hip_reduce_mx_wide(int fmt, int dtype, void* dst, const void* const* src_elems, const uint8_t* const* src_scales, int k,

@@ -145,12 +145,31 @@ inline void reduceMx(gloo_hip_mx_format_t fmt, const MxBuffer& dst, const std::v
                                     stream);
   if (rc != GLOO_HIP_OK) throw EnforceNotMet(gloo_hip_last_error());
 }
+// ... requantised with stochastic rounding from `seed` (include/gloo_amd.h "MX stochastic rounding")
+inline void reduceMx(gloo_hip_mx_format_t fmt, const MxBuffer& dst, const std::vector<MxBuffer>& srcs, size_t nblocks,
+                     uint64_t seed, hipStream_t stream) {
+  std::vector<const void*> elems;
+  std::vector<const uint8_t*> scales;
+  for (const MxBuffer& s : srcs) {
+    elems.push_back(s.elems);
+    scales.push_back(s.scales);
+  }
+  const int rc = gloo_hip_reduce_mx_sr(fmt, dst.elems, dst.scales, elems.data(), scales.data(), (int)srcs.size(), nblocks,
+                                       seed, stream);
+  if (rc != GLOO_HIP_OK) throw EnforceNotMet(gloo_hip_last_error());
+}
 // The two ends of that path for f32 / f16 / bf16 (include/gloo_amd.h "MX
 // quantise and wide-output fold"): dst = the MX form of nblocks * 32 elements
 // of `dtype` at src; neither call has an in-place form.
 inline void quantiseMx(gloo_hip_mx_format_t fmt, gloo_hip_dtype_t dtype, const MxBuffer& dst, const void* src, size_t nblocks,
                        hipStream_t stream) {
   const int rc = gloo_hip_quantise_mx(fmt, dtype, dst.elems, dst.scales, src, nblocks, stream);
+  if (rc != GLOO_HIP_OK) throw EnforceNotMet(gloo_hip_last_error());
+}
+// ... with stochastic rounding from `seed`
+inline void quantiseMx(gloo_hip_mx_format_t fmt, gloo_hip_dtype_t dtype, const MxBuffer& dst, const void* src, size_t nblocks,
+                       uint64_t seed, hipStream_t stream) {
+  const int rc = gloo_hip_quantise_mx_sr(fmt, dtype, dst.elems, dst.scales, src, nblocks, seed, stream);
   if (rc != GLOO_HIP_OK) throw EnforceNotMet(gloo_hip_last_error());
 }
 // dst = the f32 sum of srcs narrowed once to `dtype`; one source is the dequantise.

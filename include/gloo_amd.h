@@ -180,7 +180,36 @@ typedef enum {
  * Neither has an in-place form (the sizes differ): any byte shared between a
  * destination array and a source array, or between the two destination arrays
  * of the quantise, is refused.  Element arrays and wide arrays are 16-byte
- * aligned, scale arrays start at any byte, lengths are in blocks. */
+ * aligned, scale arrays start at any byte, lengths are in blocks.
+ *
+ * MX stochastic rounding (gloo_hip_quantise_mx_sr and gloo_hip_reduce_mx_sr,
+ * below): a second rounding mode of the two calls that narrow to MX elements,
+ * for gradients, which round to nearest even the same way every time.  Only
+ * the ELEMENTS step of a finite block changes; dequantise, accumulate, NaN
+ * block and scale, and the clamp and the sign rule of the elements step, are
+ * bit for bit the ones above.  For element i, the element's index in the whole
+ * tensor (block * 32 + position, whatever the tiling), with q its clamped
+ * scaled value:
+ *   neighbours   lo <= |q| <= hi, the neighbouring magnitudes of the element
+ *                type's table; lo = hi = |q| where |q| is on the grid (max
+ *                normal is).
+ *   fraction     frac = (|q| - lo) / (hi - lo), frac16 = floor(frac * 2^16);
+ *                0 where q is a binary32 denormal.
+ *   decision     the stored magnitude is hi if frac16 + R16(i) >= 2^16, else
+ *                lo; the sign is q's.  A value on the grid never moves, so a
+ *                tensor already on the grid gives the round-to-nearest bytes
+ *                for every seed.  The error of an element is below one grid
+ *                step and its expectation below 2^-16 of a step.
+ *   random bits  counter-based, from the call's uint64_t seed, so a call is
+ *                reproducible and ranks folding the same bytes with the same
+ *                seed store the same bytes.  fmix32 is MurmurHash3's
+ *                finaliser (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13;
+ *                h *= 0xC2B2AE35; h ^= h >> 16, mod 2^32).  K = fmix32(lo32(
+ *                seed)) ^ hi32(seed).  For the pair p = i >> 1, W(p) = fmix32(
+ *                (lo32(p) ^ K) + 0x9E3779B9 * hi32(p)); R16(i) is the low half
+ *                of W(i >> 1) for even i, the high half for odd i.
+ * Arguments, refusals, the in-place rule of the sum and nblocks == 0 are those
+ * of gloo_hip_quantise_mx and gloo_hip_reduce_mx. */
 typedef enum {
   GLOO_HIP_MXFP8_E4M3 = 0,
   GLOO_HIP_MXFP8_E5M2 = 1,
@@ -306,6 +335,15 @@ int gloo_hip_reduce_mx_wide(int fmt, int dtype, void* dst, const void* const* sr
  * format or a dtype that is not wide). */
 size_t gloo_hip_mx_quantise_tile_blocks(int fmt, int dtype);
 size_t gloo_hip_mx_wide_tile_blocks(int fmt, int dtype);
+
+/* gloo_hip_quantise_mx and gloo_hip_reduce_mx with stochastic rounding ("MX
+ * stochastic rounding" above) from `seed`: the same arguments, checked in the
+ * same order with the same texts under these names, the same kernels' tiles
+ * (gloo_hip_mx_quantise_tile_blocks, gloo_hip_mx_tile_blocks). */
+int gloo_hip_quantise_mx_sr(int fmt, int dtype, void* dst_elems, uint8_t* dst_scales, const void* src, size_t nblocks,
+                            uint64_t seed, gloo_hip_stream_t stream);
+int gloo_hip_reduce_mx_sr(int fmt, void* dst_elems, uint8_t* dst_scales, const void* const* src_elems,
+                          const uint8_t* const* src_scales, int k, size_t nblocks, uint64_t seed, gloo_hip_stream_t stream);
 
 /* Host-staged chunk reduction: host_dst[i] = host_dst[i] (op) host_src[i]
  * for a chunk that starts and ends in (pinned) host memory — a transport's

@@ -10,10 +10,12 @@ launches after a warm-up.  The wide tensor is `--wide-mib` MiB, so the MX side
 is 1/2 to 1/8 of that.  Wide sources rotate through six tensors (384 MiB) and
 MX sources through the slots of a 384 MiB arena, 1.5x the Infinity Cache, so
 every launch streams from HBM; destinations are buffers of their own.  All
-values are finite and the scales lie in [120, 134].  Prints one JSON line: per
-case the times of every repetition, the median, the spread (max - min) /
-median, GiB/s over the bytes read plus the bytes written, and the ratio of
-that rate to reduce_mx's.
+values are finite and the scales lie in [120, 134].  The quantise runs in both
+rounding modes, round to nearest even and stochastic (`quantise_sr`, a new seed
+per launch), in the same interleaving.  Prints one JSON line: per case the
+times of every repetition, the median, the spread (max - min) / median, GiB/s
+over the bytes read plus the bytes written, the ratio of that rate to
+reduce_mx's, and for the stochastic row its ratio to the round-to-nearest one.
   --alt-lib PATH: a second build of the library (for instance one compiled with
   -DGLOO_MX_WIDE_STORE=1) whose wide fold is timed in the same interleaving.
   python tools/mx_quant_bench.py [--reps 5] [--steps 60] [--warmup 10] [--alt-lib PATH]
@@ -72,9 +74,10 @@ def main():
                 return [arena.data_ptr() + i * eb for i in slots], [scale_arena.data_ptr() + i * nblocks for i in slots]
 
             def launch(name, k, step):
-                if name == "quantise":
+                if name in ("quantise", "quantise_sr"):
                     gloo_amd.quantise_mx_ptr(fmt, dt, mx_dst.data_ptr(), mx_dst_scales.data_ptr(),
-                                             wide[dt][step % WIDE_POOL].data_ptr(), nblocks, s)
+                                             wide[dt][step % WIDE_POOL].data_ptr(), nblocks, s,
+                                             seed=step if name == "quantise_sr" else None)
                 elif name == "reduce_mx":
                     gloo_amd.reduce_mx_ptr(fmt, mx_dst.data_ptr(), mx_dst_scales.data_ptr(), *sources(k, step), nblocks, s)
                 elif name == "wide":
@@ -87,8 +90,10 @@ def main():
                     assert rc == 0, rc
 
             for k, new in ((1, "quantise"), (2, "wide"), (8, "wide")):
-                names = (new, "reduce_mx") + (("wide_alt",) if alt and new == "wide" else ())
+                names = (new,) + (("quantise_sr",) if new == "quantise" else ()) + ("reduce_mx",)
+                names += ("wide_alt",) if alt and new == "wide" else ()
                 moved = {"quantise": wbytes + eb + nblocks, "reduce_mx": (k + 1) * (eb + nblocks)}
+                moved["quantise_sr"] = moved["quantise"]
                 moved["wide"] = moved["wide_alt"] = k * (eb + nblocks) + wbytes
                 us = {n: [] for n in names}
                 for _ in range(args.reps):
@@ -108,6 +113,8 @@ def main():
                     n: {"us": [round(t, 2) for t in us[n]], "median_us": round(med[n], 2), "gib_s": round(rate[n], 1),
                         "spread": round((max(us[n]) - min(us[n])) / med[n], 4),
                         "rate_over_reduce_mx": round(rate[n] / rate["reduce_mx"], 4)} for n in names}
+                if new == "quantise":
+                    out[f"{dt}_{fmt}_{new}_k{k}"]["quantise_sr"]["rate_over_nearest"] = round(rate["quantise_sr"] / rate[new], 4)
     print(json.dumps(out))
 
 

@@ -2,7 +2,8 @@
 """MX block-scaled sum of 64 MiB of element bytes per source beside the wide
 sum (developer tool).
 
-gloo_amd.reduce_mx for MXFP8 e4m3 and MXFP4 at k = 2 and k = 8, interleaved
+gloo_amd.reduce_mx for MXFP8 e4m3 and MXFP4 at k = 2 and k = 8, each in both
+rounding modes (`*_sr`: stochastic, a new seed per launch), interleaved
 with gloo_hip_reduce_multi SUM_WIDE on F8E4M3 at the same k and the same
 element bytes (the existing fold with the same traffic minus the 1/32 of scale
 bytes; at k = 2 that op is SUM), over `--reps` repetitions in one process:
@@ -12,7 +13,8 @@ launch streams from HBM; dst is a buffer of its own.  The elements are finite
 and the scales lie in [120, 134], so no block is a NaN block.  Prints one JSON
 line: per case the times of every repetition, the median, GiB/s over
 (k + 1) * 33/32 * element bytes (the wide sum: (k + 1) * element bytes), the
-ratio of the rates to the wide sum's and the wide sum's own spread.
+ratio of the rates to the wide sum's, the wide sum's own spread, and for a
+stochastic row its ratio to the round-to-nearest row of the same format.
   python tools/mx_reduce_bench.py [--reps 5] [--steps 60] [--warmup 10]
 """
 import argparse
@@ -55,12 +57,14 @@ def main():
             gloo_amd.reduce_multi_ptr("sum_wide", "f8e4m3", dst.data_ptr(), [elems[i].data_ptr() for i in pick], nbytes,
                                       s.cuda_stream)
         else:
-            nblocks = scales[name][0].numel()
-            gloo_amd.reduce_mx_ptr(name, dst.data_ptr(), dst_scales.data_ptr(), [elems[i].data_ptr() for i in pick],
-                                   [scales[name][i].data_ptr() for i in pick], nblocks, s.cuda_stream)
+            fmt = name[:-3] if name.endswith("_sr") else name
+            nblocks = scales[fmt][0].numel()
+            gloo_amd.reduce_mx_ptr(fmt, dst.data_ptr(), dst_scales.data_ptr(), [elems[i].data_ptr() for i in pick],
+                                   [scales[fmt][i].data_ptr() for i in pick], nblocks, s.cuda_stream,
+                                   seed=step if fmt != name else None)
 
     out = {"src_mib": args.src_mib, "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "lib": gloo_amd.LIB_PATH}
-    names = ("sum_wide", "mxfp8_e4m3", "mxfp4_e2m1")
+    names = ("sum_wide", "mxfp8_e4m3", "mxfp8_e4m3_sr", "mxfp4_e2m1", "mxfp4_e2m1_sr")
     for k in (2, 8):
         us = {n: [] for n in names}
         for _ in range(args.reps):
@@ -82,6 +86,9 @@ def main():
             case[n] = {"us": [round(t, 2) for t in us[n]], "median_us": round(med[n], 2), "gib_s": round(rate[n], 1),
                        "spread": round((max(us[n]) - min(us[n])) / med[n], 4),
                        "rate_over_sum_wide": round(rate[n] / rate["sum_wide"], 4)}
+        for n in names:
+            if n.endswith("_sr"):
+                case[n]["rate_over_nearest"] = round(rate[n] / rate[n[:-3]], 4)
         out[f"k{k}"] = case
     print(json.dumps(out))
 
